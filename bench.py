@@ -6,7 +6,14 @@ lib/hash".  One step = one launch of the batched kernel over the whole per-GPU b
 already resident in HBM (generated in place by generator G).
 
     python bench.py [--gpus N --steps K --warmup W] [--config c2|c3|c4] [--kernel auto|pc|lane]
+    python bench.py --full ...               # the line with every sub-measurement as well
+    python bench.py --dump-outputs DIR ...   # + the last timed step's digests as DIR/digests.npy
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value,
+ms_per_step, config, devices).  --full adds what takes work of its own after the timed steps:
+fixture parity, clock probe, board power, roofline / issue figures, library code hashes, the
+host-resident, config-5, C3 / C4, MD5 and CPU-baseline sub-measurements.
 
 N>1: one process per GPU, parts sharded round-robin (global part p -> rank p % N, slot
 p // N), per-GPU work fixed (weak scaling), no collective on the data path -- only a barrier
@@ -18,6 +25,7 @@ before this process makes any GPU call).
 from __future__ import annotations
 
 import argparse
+import contextlib
 import ctypes
 import json
 import os
@@ -64,6 +72,14 @@ def parse(argv=None):
     ap.add_argument("--kernel", default="auto", choices=["auto", "skew", "skewp", "skews", "quad", "pair", "pc", "lane"])
     ap.add_argument("--algo", default="sha256", choices=["sha256", "md5"],
                     help="md5: the SURVEY 8(f) Content-MD5/ETag kernel (not the metric)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything else the line can carry: "
+                         "fixture parity, clock probe, board power, roofline / issue figures, "
+                         "library code hashes, host-resident, config-5, C3 / C4, MD5 and CPU "
+                         "baseline sub-measurements (the --no-* options trim these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (the digest table a caller "
+                         "receives, one row of 32-bit words per part) as DIR/<name>.npy, float64")
     ap.add_argument("--cpu-sample-parts", type=int, default=1024)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--slice-bytes", type=int, default=0, help="host mode: bytes per part per slice")
@@ -396,7 +412,8 @@ def main():
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize(dev)
-    with power_sampler(devices[rank]) as pw:
+    # --full only: the board power / clock sampler thread beside the timed launches
+    with (power_sampler(devices[rank]) if args.full else contextlib.nullcontext()) as pw:
         t0 = time.perf_counter()
         for i in range(args.steps):
             ev[i][0].record(stream)
@@ -416,37 +433,14 @@ def main():
     wall, kern_ms_max = float(t[0]), float(t[1])
     ph.mark(f"timed {args.steps} steps")
 
-    probe = clock_probe(torch, plan, info, data, digests, stream, dev, kname)
-    power = gather_obj(dist, world, pw.summary())
-
-    # parity of the last timed step's digests against the reference fixtures, on EVERY rank
-    # (tests/golden: C2/C4 parts and four parts of each rank's shard at N = 2, 4, 8)
-    gd = digests.cpu().numpy().view(np.uint32)
-    fixtures = golden_fixtures(args.config, args.algo, args.part_bytes)
-    checked = bad = 0
-    for slot, p in enumerate(ids):
-        want = fixtures.get(int(p))
-        if want is not None:
-            checked += 1
-            bad += s3.hash_to_text(gd[slot]) != want
-    par = per_rank(dist, world, [checked, int(bad)])
-
-    key = isa_key(kname, len(lens))
-    lib_info = library_info([key])
+    # the last timed step's digest table: what a caller of the timed path receives
+    gd = digests.cpu().numpy().view(np.uint32) if (args.dump_outputs or args.full) else None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, digests=gd)
+        ph.mark("dump outputs")
     part_bytes = float(lens.sum())
     total_bytes = part_bytes * world * args.steps
     value = total_bytes / 2**30 / wall
-    algo_bytes = part_bytes + 4 * plan.words * len(lens)  # read once + digests written
-    achieved = algo_bytes / (kern_ms / 1e3) / 1e9      # GB/s, this rank's kernel
-    compressions = info["total_blocks"]
-    traffic, traffic_src, traffic_note = pmc_traffic(args.config, kname, key,
-                                                     lib_info["kernel_code_hash"].get(key),
-                                                     algo_bytes)
-    # one part = one sequential chain on one lane: report what one chain sustains and how
-    # many of the chip's 256 CU x 4 SIMD x 64 = 65,536 lanes the batch can occupy
-    chain_gbps = float(lens.max()) / (kern_ms / 1e3) / 1e9
-    issue = issue_model(kname, len(lens), kern_ms, info, probe)
-    ph.mark("parity+probe")
 
     line = None
     if rank == 0:
@@ -464,28 +458,17 @@ def main():
                        "solo_workgroups": info["solo"],
                        "parallelism": f"parts sharded round-robin over {world} GPU(s), no collective"},
             "devices": devices, "distinct_devices": distinct,
-            "parity": {"fixtures_checked": sum(r[0] for r in par),
-                       "mismatches": sum(r[1] for r in par),
-                       "per_rank": [{"rank": k, "fixtures_checked": r[0], "mismatches": r[1]}
-                                    for k, r in enumerate(par)]},
             "status": "ok: device error word clear after every launch on every rank (s3h_plan_status)",
-            "library": lib_info,
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
-                         "traffic": traffic, "traffic_source": traffic_src,
-                         "traffic_note": traffic_note,
-                         "kernel_ms": round(kern_ms, 3),
-                         "kernel_ms_max_rank": round(kern_ms_max, 3),
-                         "bytes_per_launch": int(algo_bytes),
-                         "compressions_per_launch": int(compressions),
-                         "compressions_per_s": round(compressions / (kern_ms / 1e3), 1),
-                         "per_chain_GBps": round(chain_gbps, 4),
-                         "lanes_occupied_frac": round(min(len(lens), 65536) / 65536, 5)},
-            "issue": issue,
-            "power": power[0] if world == 1 else power,
+            "full": bool(args.full),
         }
-        if world == 1:
-            line["power"].update(energy(power[0], value))
+    # Everything below is --full: a plain run prints the line above as it stands.
+    if args.full:
+        more = full_fields(args, s3, torch, dist, world, plan, info, kname, data, digests, stream,
+                           dev, ids, lens, gd, kern_ms, kern_ms_max, value, pw)
+        ph.mark("parity+probe")
+        if rank == 0:
+            line.update(more)
+    if args.full and rank == 0:
         default_c2 = (world == 1 and args.config == "c2" and args.algo == "sha256"
                       and not args.parts_per_gpu and not args.part_bytes)
         if default_c2 and not args.no_host_resident:
@@ -517,7 +500,7 @@ def main():
                 line["configs"][c] = _guard(errors, f"configs.{c}", single_gpu_config, s3,
                                             torch, dev, c, devices[0])
                 ph.mark(f"configs.{c}")
-    if world > 1 and args.config == "c2" and args.algo == "sha256":
+    if args.full and world > 1 and args.config == "c2" and args.algo == "sha256":
         del data, digests
         plan.close()
         torch.cuda.empty_cache()
@@ -549,6 +532,76 @@ def main():
         rc = max(x[0] for x in per_rank(dist, world, [rc]))
         dist.destroy_process_group()
     return rc
+
+
+def full_fields(args, s3, torch, dist, world, plan, info, kname, data, digests, stream, dev, ids,
+                lens, gd, kern_ms, kern_ms_max, value, pw) -> dict:
+    """--full: what the line says about the timed launches beyond the headline -- fixture parity
+    on every rank, the clock probe (one more launch), board power over the timed region, the
+    library's code hashes and the roofline / issue figures.  Called on EVERY rank (it gathers
+    over ranks); rank 0 merges the result into its line."""
+    probe = clock_probe(torch, plan, info, data, digests, stream, dev, kname)
+    power = gather_obj(dist, world, pw.summary())
+
+    # parity of the last timed step's digests against the reference fixtures, on EVERY rank
+    # (tests/golden: C2/C4 parts and four parts of each rank's shard at N = 2, 4, 8)
+    fixtures = golden_fixtures(args.config, args.algo, args.part_bytes)
+    checked = bad = 0
+    for slot, p in enumerate(ids):
+        want = fixtures.get(int(p))
+        if want is not None:
+            checked += 1
+            bad += s3.hash_to_text(gd[slot]) != want
+    par = per_rank(dist, world, [checked, int(bad)])
+
+    key = isa_key(kname, len(lens))
+    lib_info = library_info([key])
+    part_bytes = float(lens.sum())
+    algo_bytes = part_bytes + 4 * plan.words * len(lens)  # read once + digests written
+    achieved = algo_bytes / (kern_ms / 1e3) / 1e9      # GB/s, this rank's kernel
+    compressions = info["total_blocks"]
+    traffic, traffic_src, traffic_note = pmc_traffic(args.config, kname, key,
+                                                     lib_info["kernel_code_hash"].get(key),
+                                                     algo_bytes)
+    # one part = one sequential chain on one lane: report what one chain sustains and how
+    # many of the chip's 256 CU x 4 SIMD x 64 = 65,536 lanes the batch can occupy
+    chain_gbps = float(lens.max()) / (kern_ms / 1e3) / 1e9
+    issue = issue_model(kname, len(lens), kern_ms, info, probe)
+    more = {
+        "parity": {"fixtures_checked": sum(r[0] for r in par),
+                   "mismatches": sum(r[1] for r in par),
+                   "per_rank": [{"rank": k, "fixtures_checked": r[0], "mismatches": r[1]}
+                                for k, r in enumerate(par)]},
+        "library": lib_info,
+        "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
+                     "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
+                     "traffic": traffic, "traffic_source": traffic_src,
+                     "traffic_note": traffic_note,
+                     "kernel_ms": round(kern_ms, 3),
+                     "kernel_ms_max_rank": round(kern_ms_max, 3),
+                     "bytes_per_launch": int(algo_bytes),
+                     "compressions_per_launch": int(compressions),
+                     "compressions_per_s": round(compressions / (kern_ms / 1e3), 1),
+                     "per_chain_GBps": round(chain_gbps, 4),
+                     "lanes_occupied_frac": round(min(len(lens), 65536) / 65536, 5)},
+        "issue": issue,
+        "power": power[0] if world == 1 else power,
+    }
+    if world == 1:
+        more["power"].update(energy(power[0], value))
+    return more
+
+
+def dump_outputs(outdir: str, rank: int, **arrays) -> None:
+    """--dump-outputs DIR: each array the timed path handed back in its last step, as
+    DIR/<name>.npy (rank 0) or DIR/<name>_rank<r>.npy -- 32-bit digest words widened to float64
+    (exact), so two builds run with the same arguments compare output for output."""
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        if a is None:
+            continue
+        a = np.ascontiguousarray(a).view(np.uint32).astype(np.float64)
+        np.save(os.path.join(outdir, f"{name}.npy" if rank == 0 else f"{name}_rank{rank}.npy"), a)
 
 
 def rank_dry_run(dist, world: int, rank: int, local: int) -> int:
@@ -1377,6 +1430,8 @@ def host_mode(args, s3, torch, dist, data, ids, lens, offs, world, rank, name):
         out, m5 = run()
         times.append(time.perf_counter() - t0)
     wall = float(np.mean(times))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, digests=out, md5=m5)
     bad = _fixture_mismatches(s3, ids, out, m5, args.config, args.part_bytes)
     if rank == 0:
         what = "SHA-256 + MD5 (one H2D pass)" if dual else "SHA-256"
@@ -1428,6 +1483,8 @@ def dual_mode(args, s3, torch, data, ids, lens, offs, rank, name, stream):
         sha, m5 = s3.sha256_md5_batch_device(data, offs, lens, stream=stream)
         times.append(time.perf_counter() - t0)
     wall = float(np.mean(times))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, digests=sha.cpu().numpy(), md5=m5.cpu().numpy())
     bad = _fixture_mismatches(s3, ids, sha.cpu().numpy().view(np.uint32),
                               m5.cpu().numpy().view(np.uint32), args.config, args.part_bytes)
     if rank == 0:
@@ -1478,6 +1535,8 @@ def stream_mode(args, s3, torch, data, ids, lens, offs, rank, name, stream):
     wall = (time.perf_counter() - t0) / max(1, args.steps)
     st.status(stream)  # every update/final launch's device error word clear (raises otherwise)
     gd = out.cpu().numpy().view(np.uint32)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, digests=gd)
     fixtures = golden_fixtures(args.config, algo, args.part_bytes)
     checked = [int(p) for p in ids if int(p) in fixtures]
     bad = sum(s3.hash_to_text(gd[s]) != fixtures[int(p)]

@@ -79,9 +79,8 @@ def test_only_coissuable_instruction_classes():
 def test_shared_kernel_keeps_f32_denormals():
     """v_mul_f32 on a denormal bit pattern is a left shift only if f32 denormals are neither
     flushed on input nor on output: .amdhsa_float_denorm_mode_32 3 in the built code object."""
-    s_file = os.path.join(ROOT, "build", "isa", "capi-hip-amdgcn-amd-amdhsa-gfx950.s")
-    if not os.path.exists(s_file):
-        pytest.skip("no build/isa (make builds it)")
+    s_file = os.path.join(ROOT, "build", "isa", "launch-hip-amdgcn-amd-amdhsa-gfx950.s")
+    assert os.path.exists(s_file), "no build/isa device assembly of launch.hip (make builds it)"
     text = open(s_file).read()
     m = re.search(r"\.amdhsa_kernel _ZN3s3h25sha256_skew_shared_kernel\w*\n(.*?)\.end_amdhsa_kernel", text, re.S)
     assert m, "skews kernel descriptor not found"

@@ -192,6 +192,24 @@ def test_bench_launcher_command_touches_no_gpu():
     assert got["cmd"][-4:] == ["--gpus", "4", "--no-c4", "--print-launch"]
 
 
+def test_bench_full_and_dump_options(tmp_path):
+    """--full is off by default; --dump-outputs writes each array of 32-bit digest words as
+    float64 (exact), rank 0 under the plain name and the other ranks under <name>_rank<r>."""
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 3
+    a = bench.parse(["--full", "--dump-outputs", str(tmp_path)])
+    assert a.full is True and a.dump_outputs == str(tmp_path)
+    words = np.array([[0, 1, 0x7FFFFFFF, 0x80000000, 0xFFFFFFFF, 5, 6, 7]], dtype=np.uint32)
+    bench.dump_outputs(str(tmp_path / "d"), 0, digests=words.view(np.int32), md5=None)
+    bench.dump_outputs(str(tmp_path / "d"), 1, digests=words)
+    assert sorted(os.listdir(tmp_path / "d")) == ["digests.npy", "digests_rank1.npy"]
+    for f in ("digests.npy", "digests_rank1.npy"):
+        got = np.load(tmp_path / "d" / f)
+        assert got.dtype == np.float64 and got.shape == (1, 8)
+        assert np.array_equal(got.astype(np.uint32), words)
+
+
 def test_bench_self_launch_runs_n_ranks_on_cpu():
     """The whole self-launch on a CPU host: `bench.py --gpus 2 --rank-dry-run` starts the child
     launcher, both ranks join gloo, and the parent's stdout carries ONE line from rank 0 that

@@ -12,7 +12,7 @@ TAG=${1:?usage: power_ab.sh TAG [ROUNDS]}; ROUNDS=${2:-2}
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/../..}" || exit 1
 mkdir -p gpurun_out
 export PYTHONUNBUFFERED=1 TMPDIR=/tmp
-ARGS="--config c4 --kernel skews --steps 5 --warmup 2 --no-cpu-baseline"
+ARGS="--full --config c4 --kernel skews --steps 5 --warmup 2 --no-cpu-baseline"
 for r in $(seq 1 "$ROUNDS"); do
   for v in product pidle cidle; do
     out=gpurun_out/${TAG}_${r}_${v}.jsonl

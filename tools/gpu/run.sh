@@ -10,8 +10,10 @@
 #   pytestlib:LIB[:ARGS] the same against an experiment build (S3H_LIBRARY=LIB)
 #   smoke                __graft_entry__.smoke()                              (120 s)
 #   bench[:ARGS]         python bench.py ARGS -> one JSON line                (400 s)
+#                        (ARGS with --full for parity, roofline, library and the sub-measurements;
+#                        the same holds for benchlib, pmc, pmclib, n2 and selfn)
 #   benchlib:LIB[:ARGS]  the same with S3H_LIBRARY=LIB (a `make exp` build)    (400 s)
-#   stats[:ARGS]         rocprofv3 --kernel-trace --stats of bench.py ARGS    (400 s)
+#   stats[:ARGS]         rocprofv3 --kernel-trace --stats of bench.py --full ARGS (400 s)
 #   pmc[:CTRS[:ARGS]]    rocprofv3 --pmc CTRS (one pass, e.g. FETCH_SIZE) of bench.py ARGS (240 s)
 #   pmclib:LIB:CTRS[:ARGS] the same on an experiment build (S3H_LIBRARY=LIB)     (240 s)
 #   n2[:ARGS]            2-rank torch.distributed.run rehearsal of bench.py on the one GPU
@@ -52,7 +54,7 @@ for step in "$@"; do
       S3H_LIBRARY=$lib timeout -k 10 400 python bench.py $args > $out.jsonl 2> $out.err; rc=$?
       [ $rc -eq 0 ] && python3 tools/gpu/summary.py $out.jsonl ;;
     stats)
-      timeout -k 10 400 rocprofv3 --kernel-trace --stats -d ${out}_prof -o run --output-format csv -- python3 bench.py $rest > $out.jsonl 2> $out.err; rc=$?
+      timeout -k 10 400 rocprofv3 --kernel-trace --stats -d ${out}_prof -o run --output-format csv -- python3 bench.py --full $rest > $out.jsonl 2> $out.err; rc=$?
       [ $rc -eq 0 ] && head -4 ${out}_prof/run_kernel_stats.csv | cut -c1-200 ;;
     pmc)
       ctrs=${rest%%:*}; args=""; [ "$rest" != "$ctrs" ] && args=${rest#*:}

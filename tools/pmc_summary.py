@@ -5,7 +5,7 @@
         --bytes-per-launch B --bench-jsonl LINE --kernel-key skew --out profiles/r03_c2_skew_pmc.json
 
 Provenance: the summary records the kernel's code hash and the library sha256 that the
-profiled bench run loaded (its JSON line's `library` object, --bench-jsonl) and the git commit
+profiled `bench.py --full` run loaded (its JSON line's `library` object, --bench-jsonl) and the git commit
 it was summarised at; bench.py uses a profile's traffic only for a build whose kernel code
 hash is the same (pmc_traffic).
 
@@ -44,7 +44,7 @@ def main():
     ap.add_argument("--bytes-per-launch", type=float, required=True)
     ap.add_argument("--out", required=True)
     ap.add_argument("--bench-jsonl", required=True,
-                    help="the profiled bench.py run's output (its `library` object)")
+                    help="the profiled `bench.py --full` run's output (its `library` object)")
     ap.add_argument("--kernel-key", required=True, help="tools/isa_counts.py ALL_KERNELS key")
     a = ap.parse_args()
     fetch = mean(per_dispatch(a.fetch, a.kernel), "FETCH_SIZE")

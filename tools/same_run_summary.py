@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-launch kernel times of the default bench line's own rocprofv3 run (tools/gpu/run.sh
-`stats`): `rocprofv3 --kernel-trace --stats -- python3 bench.py` writes the trace, and the
+`stats`): `rocprofv3 --kernel-trace --stats -- python3 bench.py --full` writes the trace, and the
 bench line it printed is the SAME process's.  Groups the trace by kernel and grid (the C2 skew
 launches are the 128-workgroup sha256_skew_kernel<1> dispatches of ~121 ms; host-path slice
 launches share the symbol but not the duration) and sets each group's mean beside the line's
@@ -42,7 +42,7 @@ def main():
     # C2: 1,024 parts on the skew kernel = 128 workgroups of 128 threads (consumer + producer)
     c2 = launches(trace, "sha256_skew_kernel<1, false>", grid_x=128 * 128, min_ms=50.0)
     s = stats(c2)
-    res = {"what": "rocprofv3 --kernel-trace --stats of `python3 bench.py` (the default N=1 line); "
+    res = {"what": "rocprofv3 --kernel-trace --stats of `python3 bench.py --full` (the N=1 line); "
                    "per-launch durations from its kernel trace, the line from the same process",
            "commit": subprocess.run(["git", "rev-parse", "--short=12", "HEAD"], capture_output=True,
                                     text=True).stdout.strip(),
