@@ -31,7 +31,9 @@ extern "C" {
 
 /* 2: s3h_route_rates_t / s3h_route_choose (size-carrying, digest sets), s3h_host_plan,
  * s3h_host_alloc_ex, MD5 and dual routed entry points.  s3h_route_model_t keeps its round-5
- * layout (8 fields) for good: new rates go to s3h_route_rates_t, which carries its size. */
+ * layout (8 fields) for good: new rates go to s3h_route_rates_t, which carries its size.
+ * Added within version 2 (new symbols only, nothing changed): the CRC-32C / CRC-32 entry
+ * points (s3h_crc_*, s3h_cpu_crc, s3h_checksum_text). */
 #define S3H_API_VERSION 2
 
 enum s3h_status {
@@ -515,6 +517,55 @@ int s3h_stream_stats(s3h_stream_t s, uint64_t *slot_reuses, uint64_t *slot_refil
 /* Bytes appended so far to message i (host bookkeeping; no device sync). */
 int s3h_stream_total(s3h_stream_t s, uint64_t i, uint64_t *total);
 int s3h_stream_destroy(s3h_stream_t s);
+
+/* ---------------------------------------------------------------- CRC-32C / CRC-32 checksums
+ * S3's "additional checksums" (x-amz-checksum-crc32c / x-amz-checksum-crc32 on UploadPart, the
+ * full-object or composite value on CompleteMultipartUpload; <ChecksumAlgorithm> in
+ * lib/src/api/xml_parser.cpp:94) for device-resident parts.  Both are reflected 32-bit CRCs
+ * with init and xor-out 0xFFFFFFFF: CRC-32C = Castagnoli (0x82F63B78), CRC-32 = ISO-HDLC /
+ * zlib (0xEDB88320).  Output layout (every entry point): one uint32 per part, in part order,
+ * holding the CRC's numeric value (what zlib.crc32 returns); a part of length 0 gives 0.
+ *
+ * A CRC is linear, so each part is cut into segments (s3h_crc_plan_info: segment_bytes, chosen
+ * by the plan from the batch) that are checksummed independently -- one wave each -- and folded
+ * per part by a second launch: a single large part uses the whole GPU.  Offsets may have any
+ * byte alignment.  The segment values live in a buffer the plan owns: launch one plan on ONE
+ * stream at a time (as for s3h_plan_launch); launches on one stream may follow each other
+ * without a sync.  Host-resident data: s3h_cpu_crc (a CRC alone from host memory is bounded by
+ * the host link, below what a few cores reach).  Added within API version 2. */
+enum s3h_crc { S3H_CRC32C = 0, S3H_CRC32 = 1 };
+typedef struct s3h_crc_plan_s *s3h_crc_plan_t;
+int s3h_crc_plan_create(int device, int crc, const uint64_t *offsets, const uint64_t *lengths,
+                        uint64_t n, s3h_crc_plan_t *plan);
+/* Asynchronous on `stream`: d_crcs (n words, device) is complete when the stream reaches it. */
+int s3h_crc_plan_launch(s3h_crc_plan_t plan, const void *d_base, uint32_t *d_crcs, void *stream);
+/* n parts, segments in all, bytes per segment, workgroups of the segment launch (any may be null). */
+int s3h_crc_plan_info(s3h_crc_plan_t plan, uint64_t *n, uint64_t *segments, uint64_t *segment_bytes,
+                      uint32_t *grid);
+int s3h_crc_plan_destroy(s3h_crc_plan_t plan);
+/* One-shot, blocking: plan + launch + sync. */
+int s3h_crc_batch_device(int device, int crc, const void *d_base, const uint64_t *offsets,
+                         const uint64_t *lengths, uint64_t n, uint32_t *d_crcs, void *stream);
+/* As s3h_verify_batch_device, against n expected CRCs (device).  Blocking. */
+int s3h_crc_verify_batch_device(int device, int crc, const void *d_base, const uint64_t *offsets,
+                                const uint64_t *lengths, uint64_t n, const uint32_t *d_expected,
+                                uint8_t *d_mismatch, uint64_t *mismatches, void *stream);
+/* CPU, one message.  seed_crc: 0, or a previous call's result, so chunks chain like zlib's
+ * crc32(data, seed).  CRC-32C uses the SSE4.2 instruction where the CPU has it
+ * (S3H_CPU_SCALAR=1 forces the table path).  Unknown `crc`: returns 0 and sets s3h_last_error. */
+uint32_t s3h_cpu_crc(int crc, const uint8_t *data, uint64_t length, uint32_t seed_crc);
+/* crc(A || B) from crc(A), crc(B) and |B| (zlib's crc32_combine), without the data. */
+int s3h_crc_combine(int crc, uint32_t crc_a, uint32_t crc_b, uint64_t len_b, uint32_t *out);
+/* FULL_OBJECT checksum: the CRC of the n parts' concatenation from their CRCs and lengths. */
+int s3h_crc_object(int crc, const uint32_t *part_crcs, const uint64_t *lengths, uint64_t n,
+                   uint32_t *out);
+/* Header text, NUL-terminated, out_len >= S3H_CHECKSUM_MAX.  composite = 0: n must be 1, the
+ * value of x-amz-checksum-crc32c / -crc32 (base64 of the CRC's 4 bytes, big-endian) -- of a
+ * part, or of s3h_crc_object's result for the FULL_OBJECT form.  composite = 1: the COMPOSITE
+ * form, base64 of the CRC of the n big-endian part CRCs concatenated, then "-n". */
+#define S3H_CHECKSUM_MAX 32
+int s3h_checksum_text(int crc, const uint32_t *part_crcs, uint64_t n, int composite, char *out,
+                      uint64_t out_len);
 
 /* ---------------------------------------------------------------- synthetic inputs
  * Fill part i (at d_base + offsets[i], 8-B aligned, lengths[i] bytes) with generator

@@ -276,3 +276,54 @@ inline std::string multipart_etag(const std::vector<uint32_t>& part_md5s) {
 }
 
 }  // namespace md5
+
+// S3 "additional checksums" (x-amz-checksum-crc32c / x-amz-checksum-crc32): `algo` is
+// S3H_CRC32C or S3H_CRC32, every value the CRC's number (one uint32_t per part).
+namespace crc {
+
+// Parts already in device memory at d_base + offsets[i] (any alignment); n CRCs to d_crcs.
+inline void crc_batch_device(int device, int algo, const void* d_base,
+                             const std::vector<uint64_t>& offsets,
+                             const std::vector<uint64_t>& lengths, uint32_t* d_crcs,
+                             void* stream = nullptr) {
+  if (offsets.size() != lengths.size()) throw std::invalid_argument("offsets/lengths size mismatch");
+  sha256::batch_check(s3h_crc_batch_device(device, algo, d_base, offsets.data(), lengths.data(),
+                                           offsets.size(), d_crcs, stream));
+}
+
+// One message on the CPU; `seed` = a previous call's result (chunks chain like zlib's).
+inline uint32_t crc(int algo, const uint8_t* data, uint64_t length, uint32_t seed = 0) {
+  if (algo != S3H_CRC32C && algo != S3H_CRC32) throw std::invalid_argument("crc: unknown checksum");
+  return s3h_cpu_crc(algo, data, length, seed);
+}
+
+inline uint32_t combine(int algo, uint32_t crc_a, uint32_t crc_b, uint64_t len_b) {
+  uint32_t out = 0;
+  sha256::batch_check(s3h_crc_combine(algo, crc_a, crc_b, len_b, &out));
+  return out;
+}
+
+// The FULL_OBJECT checksum of a multipart upload from its parts' CRCs and lengths.
+inline uint32_t object_crc(int algo, const std::vector<uint32_t>& part_crcs,
+                           const std::vector<uint64_t>& lengths) {
+  if (part_crcs.size() != lengths.size()) throw std::invalid_argument("crcs/lengths size mismatch");
+  uint32_t out = 0;
+  sha256::batch_check(s3h_crc_object(algo, part_crcs.data(), lengths.data(), part_crcs.size(), &out));
+  return out;
+}
+
+// Header value of one CRC (a part's, or object_crc's result): base64 of its big-endian bytes.
+inline std::string checksum_text(int algo, uint32_t value) {
+  char out[S3H_CHECKSUM_MAX];
+  sha256::batch_check(s3h_checksum_text(algo, &value, 1, 0, out, sizeof out));
+  return out;
+}
+
+// The COMPOSITE checksum of a multipart upload: "<base64>-<parts>".
+inline std::string composite_checksum_text(int algo, const std::vector<uint32_t>& part_crcs) {
+  char out[S3H_CHECKSUM_MAX];
+  sha256::batch_check(s3h_checksum_text(algo, part_crcs.data(), part_crcs.size(), 1, out, sizeof out));
+  return out;
+}
+
+}  // namespace crc

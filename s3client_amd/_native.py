@@ -48,7 +48,14 @@ C_ABI_SYMBOLS = (
     "s3h_route_scale", "s3h_md5_batch_routed", "s3h_sha256_md5_batch_routed",
     "s3h_sha256_md5_file_parts_routed", "s3h_md5_file_parts", "s3h_host_plan",
     "s3h_host_alloc_ex", "s3h_device_power_cap", "s3h_pci_power_cap",
+    # CRC-32C / CRC-32 checksums (added within API version 2)
+    "s3h_crc_plan_create", "s3h_crc_plan_launch", "s3h_crc_plan_info", "s3h_crc_plan_destroy",
+    "s3h_crc_batch_device", "s3h_crc_verify_batch_device", "s3h_cpu_crc", "s3h_crc_combine",
+    "s3h_crc_object", "s3h_checksum_text",
 )
+CRC32C, CRC32 = 0, 1
+CRC_IDS = {"crc32c": CRC32C, "crc32": CRC32}
+CHECKSUM_MAX = 32
 POLICY_IDS = {"throughput": 0, "efficiency": 1, "power": 2}
 POLICY_NAMES = {v: k for k, v in POLICY_IDS.items()}
 SOURCE_IDS = {"pinned": 0, "pageable": 1, "file": 2}
@@ -315,6 +322,27 @@ def lib() -> ctypes.CDLL:
             L.s3h_stream_final_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
             L.s3h_stream_total.argtypes = [ctypes.c_void_p, ctypes.c_uint64, u64p]
             L.s3h_stream_destroy.argtypes = [ctypes.c_void_p]
+            L.s3h_crc_plan_create.argtypes = [ctypes.c_int, ctypes.c_int, u64p, u64p,
+                                              ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p)]
+            L.s3h_crc_plan_launch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_void_p]
+            L.s3h_crc_plan_info.argtypes = [ctypes.c_void_p, u64p, u64p, u64p, u32p]
+            L.s3h_crc_plan_destroy.argtypes = [ctypes.c_void_p]
+            L.s3h_crc_batch_device.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, u64p,
+                                               u64p, ctypes.c_uint64, ctypes.c_void_p,
+                                               ctypes.c_void_p]
+            L.s3h_crc_verify_batch_device.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                                      u64p, u64p, ctypes.c_uint64, ctypes.c_void_p,
+                                                      ctypes.c_void_p, u64p, ctypes.c_void_p]
+            L.s3h_cpu_crc.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
+                                      ctypes.c_uint32]
+            L.s3h_cpu_crc.restype = ctypes.c_uint32
+            L.s3h_crc_combine.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32,
+                                          ctypes.c_uint64, u32p]
+            L.s3h_crc_object.argtypes = [ctypes.c_int, ctypes.c_void_p, u64p, ctypes.c_uint64,
+                                         u32p]
+            L.s3h_checksum_text.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
+                                            ctypes.c_int, ctypes.c_char_p, ctypes.c_uint64]
             _lib = L
     return _lib
 

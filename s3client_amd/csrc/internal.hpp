@@ -3,11 +3,12 @@
 // unit with device code), pinned host memory and device placement (pinned.cpp), and the
 // stream units' hooks.  The C-ABI itself is include/s3hash.h.
 //
-//   launch.hip    sha256_kernels.hip + the hipLaunchKernelGGL calls (device code)
+//   launch.hip    sha256_kernels.hip + crc32_kernels.hip + the hipLaunchKernelGGL calls (device code)
 //   plan.cpp      plans: kernel choice, slot sorting, launches, error words; device-resident C-ABI
 //   pinned.cpp    NUMA-placed pinned host memory, device placement, s3h_host_alloc / _numa
 //   host_path.cpp host-resident pipeline (slices, groups), per-device contexts, the merge queue
 //   stream.cpp    multi-object streams (s3h_stream_*)
+//   crc.cpp       CRC-32C / CRC-32 plans of device-resident parts (s3h_crc_*)
 //   route.cpp     size-aware routing (model measurement, observed rates, routed entry points)
 //   HIP-free: status.cpp, topology.cpp, route_plan.cpp (+ copy_pool.hpp, host_queue.hpp)
 #pragma once
@@ -126,6 +127,10 @@ hipError_t launch_compare_digests(const uint32_t* got, const uint32_t* want, uin
                                   hipStream_t s);
 hipError_t launch_generate(uint8_t* base, const s3h::GenPart* parts, uint32_t nparts, uint32_t gx,
                            uint64_t seed, hipStream_t s);
+
+// CRC stage 1 (skipped when there is no segment) then stage 2, both on `s`.
+hipError_t launch_crc(const s3h::CrcSegArgs& A, uint32_t seg_grid, const s3h::CrcPartArgs& B,
+                      hipStream_t s);
 
 // ------------------------------------------------------------------ host memory (pinned.cpp)
 // Pinned host memory whose pages live on `node` (< 0: the runtime's hipHostMalloc).

@@ -97,6 +97,38 @@ struct SpliceJob {
 };
 constexpr uint32_t kSpliceHead = 1, kSpliceGrow = 2, kSpliceReset = 4;
 
+// ------------------------------------------------------------- CRC-32C / CRC-32 (crc32_kernels.hip)
+// Stage 1 (crc_segments_kernel): one record per segment of a non-empty part, in part order.
+struct CrcSeg {
+  uint64_t off;   // byte offset of the segment relative to the launch's base pointer
+  uint32_t len;   // 1..segment_bytes
+  uint32_t pad_;
+};
+// Stage 2 (crc_parts_kernel): part p's ceil(len / segment_bytes) values start at partials[seg0].
+struct CrcPart {
+  uint64_t seg0;
+  uint64_t len;
+};
+struct CrcSegArgs {
+  const uint8_t* base;
+  const CrcSeg* segs;
+  const uint32_t* tables;  // crc_math.hpp build_device_tables (kTableWords words, 16-B aligned)
+  uint32_t* partials;      // one raw value per segment
+  uint64_t nseg;
+  uint32_t poly;
+};
+struct CrcPartArgs {
+  const CrcPart* parts;
+  const uint32_t* partials;
+  uint32_t* crcs;          // one finalised CRC per part, part order
+  uint64_t n;
+  uint32_t poly;
+  uint32_t x_segment;      // x^(8 * segment_bytes) mod P
+  uint32_t log2_segment;
+};
+constexpr int kCrcSegThreads = 512;   // 8 waves share one copy of the tables in LDS
+constexpr int kCrcPartThreads = 256;  // 4 parts per workgroup
+
 // ------------------------------------------------------------- synthetic input generator
 // G(seed, p, L) of SURVEY.md 8(d): one record per part (byte offset, length, generator id).
 struct GenPart { uint64_t off, len, id; };

@@ -1,10 +1,11 @@
 // launch.hip -- the only translation unit with device code: the gfx950 kernels of
-// sha256_kernels.hip and the launches that pick among them.  Everything around the launches --
+// sha256_kernels.hip and crc32_kernels.hip and the launches that pick among them.  Everything around the launches --
 // plans, the host pipeline, streams, routing -- is host C++ in the other units (internal.hpp).
 #include <hip/hip_runtime.h>
 
 #include "internal.hpp"
 #include "sha256_kernels.hip"
+#include "crc32_kernels.hip"
 
 namespace s3h::host {
 
@@ -98,6 +99,16 @@ hipError_t launch_compare_digests(const uint32_t* got, const uint32_t* want, uin
 hipError_t launch_generate(uint8_t* base, const s3h::GenPart* parts, uint32_t nparts, uint32_t gx,
                            uint64_t seed, hipStream_t s) {
   hipLaunchKernelGGL(s3h::generate_kernel, dim3(gx, nparts), dim3(256), 0, s, base, parts, seed);
+  return hipGetLastError();
+}
+
+hipError_t launch_crc(const s3h::CrcSegArgs& A, uint32_t seg_grid, const s3h::CrcPartArgs& B,
+                      hipStream_t s) {
+  if (A.nseg != 0)  // (a batch of empty parts has no segments)
+    hipLaunchKernelGGL(s3h::crc_segments_kernel, dim3(seg_grid), dim3(s3h::kCrcSegThreads), 0, s, A);
+  constexpr uint64_t per_wg = s3h::kCrcPartThreads / 64;
+  hipLaunchKernelGGL(s3h::crc_parts_kernel, dim3(uint32_t((B.n + per_wg - 1) / per_wg)),
+                     dim3(s3h::kCrcPartThreads), 0, s, B);
   return hipGetLastError();
 }
 

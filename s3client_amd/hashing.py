@@ -340,6 +340,140 @@ def verify_batch_device(data, offsets, lengths, expected, algo: str = "sha256", 
     return cnt.value, mism.bool()
 
 
+# ------------------------------------------------------------------ CRC-32C / CRC-32 checksums
+def _crc_id(algo) -> int:
+    return algo if isinstance(algo, int) else _native.CRC_IDS[algo]
+
+
+class CrcPlan:
+    """Segment geometry of one batch of device-resident parts for CRC-32C / CRC-32
+    (s3h_crc_plan_create).  One plan runs on one stream at a time: its segment values pass
+    through a buffer the plan owns."""
+
+    def __init__(self, offsets: Sequence[int], lengths: Sequence[int], device: int = 0,
+                 algo: str | int = "crc32c"):
+        self.crc = _crc_id(algo)
+        self.offsets, self.lengths = _u64(offsets), _u64(lengths)
+        if self.offsets.shape != self.lengths.shape or self.offsets.ndim != 1:
+            raise ValueError("offsets and lengths must be 1-D and of equal length")
+        self.n = int(self.lengths.size)
+        self.device = device
+        h = ctypes.c_void_p()
+        check(lib().s3h_crc_plan_create(device, self.crc, _p64(self.offsets), _p64(self.lengths),
+                                        self.n, ctypes.byref(h)))
+        self._h = h
+
+    def info(self) -> dict:
+        n, segs, sb, g = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint32()
+        check(lib().s3h_crc_plan_info(self._h, ctypes.byref(n), ctypes.byref(segs),
+                                      ctypes.byref(sb), ctypes.byref(g)))
+        return {"n": n.value, "segments": segs.value, "segment_bytes": sb.value, "grid": g.value}
+
+    def launch(self, data, crcs, stream=None) -> None:
+        """CRC of every part of ``data`` (device tensor) into ``crcs`` (n 32-bit words, device).
+        Asynchronous on ``stream``."""
+        if not (data.is_cuda and crcs.is_cuda):
+            raise ValueError("data and crcs must be device tensors")
+        if crcs.numel() * crcs.element_size() < 4 * self.n:
+            raise ValueError("crcs buffer too small (need n*4 bytes)")
+        end = int((self.offsets + self.lengths).max()) if self.n else 0
+        if data.numel() * data.element_size() < end:
+            raise ValueError(f"data buffer ({data.numel() * data.element_size()} B) smaller "
+                             f"than the plan's extent ({end} B)")
+        check(lib().s3h_crc_plan_launch(self._h, ctypes.c_void_p(data.data_ptr()),
+                                        ctypes.c_void_p(crcs.data_ptr()),
+                                        ctypes.c_void_p(_stream_handle(stream))))
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            lib().s3h_crc_plan_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def crc_batch_device(data, offsets, lengths, algo: str | int = "crc32c", stream=None):
+    """CRC-32C / CRC-32 of every part [offsets[i], offsets[i]+lengths[i]) of the device tensor
+    ``data`` (any byte alignment): an (n,) int32 device tensor holding the uint32 values
+    (``.cpu().numpy().view(np.uint32)``), what zlib.crc32 returns for CRC-32.  Blocking."""
+    import torch
+    offs, lens = _u64(offsets), _u64(lengths)
+    end = int((offs + lens).max()) if offs.size else 0
+    if not data.is_cuda or data.numel() * data.element_size() < end:
+        raise ValueError("data must be a device tensor that covers every part")
+    out = torch.empty(offs.size, dtype=torch.int32, device=data.device)
+    check(lib().s3h_crc_batch_device(data.device.index, _crc_id(algo),
+                                     ctypes.c_void_p(data.data_ptr()), _p64(offs), _p64(lens),
+                                     offs.size, ctypes.c_void_p(out.data_ptr()),
+                                     ctypes.c_void_p(_stream_handle(stream))))
+    return out
+
+
+def crc_verify_batch_device(data, offsets, lengths, expected, algo: str | int = "crc32c",
+                            stream=None):
+    """Device-resident verification against ``expected`` (n 32-bit words, device): returns
+    (mismatch count, bool mask on the device)."""
+    import torch
+    offs, lens = _u64(offsets), _u64(lengths)
+    mism = torch.zeros(offs.size, dtype=torch.uint8, device=data.device)
+    cnt = ctypes.c_uint64(0)
+    check(lib().s3h_crc_verify_batch_device(data.device.index, _crc_id(algo),
+                                            ctypes.c_void_p(data.data_ptr()), _p64(offs),
+                                            _p64(lens), offs.size,
+                                            ctypes.c_void_p(expected.data_ptr()),
+                                            ctypes.c_void_p(mism.data_ptr()), ctypes.byref(cnt),
+                                            ctypes.c_void_p(_stream_handle(stream))))
+    return cnt.value, mism.bool()
+
+
+def crc(data, algo: str | int = "crc32c", seed: int = 0) -> int:
+    """CPU CRC of one message (s3h_cpu_crc); ``seed`` = a previous call's result, so chunks
+    chain like zlib.crc32(data, seed)."""
+    a = _as_bytes(data) if isinstance(data, np.ndarray) else np.frombuffer(bytes(data), dtype=np.uint8)
+    return int(lib().s3h_cpu_crc(_crc_id(algo), ctypes.c_void_p(a.ctypes.data if a.size else None),
+                                 a.size, seed & 0xFFFFFFFF))
+
+
+def crc_combine(crc_a: int, crc_b: int, len_b: int, algo: str | int = "crc32c") -> int:
+    """crc(A || B) from crc(A), crc(B) and len(B) (s3h_crc_combine)."""
+    out = ctypes.c_uint32()
+    check(lib().s3h_crc_combine(_crc_id(algo), crc_a & 0xFFFFFFFF, crc_b & 0xFFFFFFFF,
+                                int(len_b), ctypes.byref(out)))
+    return out.value
+
+
+def crc_object(part_crcs, lengths, algo: str | int = "crc32c") -> int:
+    """FULL_OBJECT checksum of the parts' concatenation from their CRCs and lengths."""
+    w = np.ascontiguousarray(part_crcs).astype(np.uint32, copy=False).reshape(-1)
+    lens = _u64(lengths)
+    if lens.shape != w.shape:
+        raise ValueError("one length per part checksum")
+    out = ctypes.c_uint32()
+    check(lib().s3h_crc_object(_crc_id(algo), ctypes.c_void_p(w.ctypes.data), _p64(lens), w.size,
+                               ctypes.byref(out)))
+    return out.value
+
+
+def checksum_text(part_crcs, algo: str | int = "crc32c", composite: bool = False) -> str:
+    """Header text of a checksum (s3h_checksum_text): base64 of one CRC's big-endian bytes, or
+    with ``composite`` the S3 composite form of the parts' CRCs, "<base64>-<n>"."""
+    w = np.ascontiguousarray(np.atleast_1d(part_crcs)).astype(np.uint32, copy=False).reshape(-1)
+    out = ctypes.create_string_buffer(_native.CHECKSUM_MAX)
+    check(lib().s3h_checksum_text(_crc_id(algo), ctypes.c_void_p(w.ctypes.data), w.size,
+                                  int(bool(composite)), out, len(out)))
+    return out.value.decode()
+
+
 def multipart_etag(part_md5s) -> str:
     """S3 multipart ETag: hex(MD5(concatenated binary part MD5s)) + "-" + part count
     (s3h_multipart_etag; the outer MD5, 16 B per part, runs on the lib/hash MD5 drop-in)."""

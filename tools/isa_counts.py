@@ -49,6 +49,9 @@ ALL_KERNELS = {
     "dual_group": "_ZN3s3h23sha256_md5_group_kernelILb1EEEvNS_10LaunchArgsES1_",
     "dual_group_skew": "_ZN3s3h23sha256_md5_group_kernelILb0EEEvNS_10LaunchArgsES1_",
     "dual_group_mixed": "_ZN3s3h29sha256_md5_group_mixed_kernelENS_10LaunchArgsES0_jjjPmj",
+    # CRC-32C / CRC-32 (crc32_kernels.hip): code hashes only, no chain loop to count
+    "crc_segments": "_ZN3s3h19crc_segments_kernelENS_10CrcSegArgsE",
+    "crc_parts": "_ZN3s3h16crc_parts_kernelENS_11CrcPartArgsE",
 }
 FLAG_KERNELS = ("skew_nc2", "skews", "dual_group", "dual_group_skew", "dual_group_mixed")
 ERR_STORE = re.compile(r"^\t(global|flat|buffer)_atomic_or\b")
