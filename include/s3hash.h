@@ -33,7 +33,8 @@ extern "C" {
  * s3h_host_alloc_ex, MD5 and dual routed entry points.  s3h_route_model_t keeps its round-5
  * layout (8 fields) for good: new rates go to s3h_route_rates_t, which carries its size.
  * Added within version 2 (new symbols only, nothing changed): the CRC-32C / CRC-32 entry
- * points (s3h_crc_*, s3h_cpu_crc, s3h_checksum_text). */
+ * points (s3h_crc_*, s3h_cpu_crc, s3h_checksum_text), then s3h_crc_plan_launch_range and the
+ * host-resident forms s3h_crc_batch_host, s3h_sha256_crc_batch_host, s3h_sha256_crc_file_parts. */
 #define S3H_API_VERSION 2
 
 enum s3h_status {
@@ -531,14 +532,31 @@ int s3h_stream_destroy(s3h_stream_t s);
  * per part by a second launch: a single large part uses the whole GPU.  Offsets may have any
  * byte alignment.  The segment values live in a buffer the plan owns: launch one plan on ONE
  * stream at a time (as for s3h_plan_launch); launches on one stream may follow each other
- * without a sync.  Host-resident data: s3h_cpu_crc (a CRC alone from host memory is bounded by
- * the host link, below what a few cores reach).  Added within API version 2. */
+ * without a sync.  Host-resident data: s3h_sha256_crc_batch_host / s3h_sha256_crc_file_parts
+ * below give the CRC out of the SHA-256 pass (each part crosses the host link once), and
+ * s3h_crc_batch_host the CRC alone; s3h_cpu_crc is the CPU function (a CRC alone from host
+ * memory is bounded by the host link, which a few cores match for CRC-32C but not for CRC-32,
+ * which has no CPU instruction).  Added within API version 2. */
 enum s3h_crc { S3H_CRC32C = 0, S3H_CRC32 = 1 };
 typedef struct s3h_crc_plan_s *s3h_crc_plan_t;
 int s3h_crc_plan_create(int device, int crc, const uint64_t *offsets, const uint64_t *lengths,
                         uint64_t n, s3h_crc_plan_t *plan);
 /* Asynchronous on `stream`: d_crcs (n words, device) is complete when the stream reaches it. */
 int s3h_crc_plan_launch(s3h_crc_plan_t plan, const void *d_base, uint32_t *d_crcs, void *stream);
+/* Resumable form (as s3h_plan_launch_range, in bytes): process bytes [byte_begin, byte_end) of
+ * every part, where part p's byte b lives at d_base + offsets[p] + (b - byte_origin).  Each
+ * part's running value is kept in the plan between launches (same stream order required).
+ * A part's CRC is written to d_crcs[p] by the launch whose range holds its last byte.
+ * A part of length 0 is written by a launch with byte_begin == 0.  No other entry of d_crcs
+ * is touched.  A launch with byte_begin == 0 starts over.  Otherwise byte_begin must equal
+ * the previous ranged launch's byte_end (S3H_EINVAL if not, or if byte_begin >= byte_end or
+ * byte_origin > byte_begin).  Any byte values: no alignment is required of the range, the
+ * offsets or the base.  A launch allocates nothing, uploads nothing and does not wait for
+ * the device.  s3h_crc_plan_launch leaves the running values unspecified: the next ranged
+ * launch after one must begin at 0.  Asynchronous on `stream`. */
+int s3h_crc_plan_launch_range(s3h_crc_plan_t plan, const void *d_base, uint32_t *d_crcs,
+                              uint64_t byte_begin, uint64_t byte_end, uint64_t byte_origin,
+                              void *stream);
 /* n parts, segments in all, bytes per segment, workgroups of the segment launch (any may be null). */
 int s3h_crc_plan_info(s3h_crc_plan_t plan, uint64_t *n, uint64_t *segments, uint64_t *segment_bytes,
                       uint32_t *grid);
@@ -550,6 +568,21 @@ int s3h_crc_batch_device(int device, int crc, const void *d_base, const uint64_t
 int s3h_crc_verify_batch_device(int device, int crc, const void *d_base, const uint64_t *offsets,
                                 const uint64_t *lengths, uint64_t n, const uint32_t *d_expected,
                                 uint8_t *d_mismatch, uint64_t *mismatches, void *stream);
+/* Host-resident parts (pinned or pageable memory, or byte ranges of a file), arguments as for
+ * s3h_sha256_batch_host / s3h_sha256_md5_batch_host / s3h_sha256_md5_file_parts: every slice
+ * crosses the host link once and is hashed from the HBM ring by SHA-256 and by a ranged CRC
+ * launch on streams of their own.  `crc` is an enum s3h_crc; `crcs` receives n words in part
+ * order.  The route is the GPU (never a CPU fallback: no visible device is S3H_ENODEV); an
+ * unknown `crc` or a null pointer is S3H_EINVAL.  Blocking.  Concurrent callers that ask for
+ * the same digests are merged into one batch, as for the SHA-256 forms. */
+int s3h_crc_batch_host(int crc, const uint8_t *const *parts, const uint64_t *lengths, uint64_t n,
+                       uint32_t *crcs, int ndevices, uint64_t slice_bytes);
+int s3h_sha256_crc_batch_host(int crc, const uint8_t *const *parts, const uint64_t *lengths,
+                              uint64_t n, uint32_t *sha256_digests, uint32_t *crcs,
+                              int ndevices, uint64_t slice_bytes);
+int s3h_sha256_crc_file_parts(int crc, const char *path, const uint64_t *offsets,
+                              const uint64_t *lengths, uint64_t n, uint32_t *sha256_digests,
+                              uint32_t *crcs, int ndevices, uint64_t slice_bytes);
 /* CPU, one message.  seed_crc: 0, or a previous call's result, so chunks chain like zlib's
  * crc32(data, seed).  CRC-32C uses the SSE4.2 instruction where the CPU has it
  * (S3H_CPU_SCALAR=1 forces the table path).  Unknown `crc`: returns 0 and sets s3h_last_error. */

@@ -291,6 +291,46 @@ inline void crc_batch_device(int device, int algo, const void* d_base,
                                            offsets.size(), d_crcs, stream));
 }
 
+// Host-resident parts on the GPUs (s3h_crc_batch_host): one CRC per part.
+inline std::vector<uint32_t> crc_batch(int algo, const std::vector<const uint8_t*>& parts,
+                                       const std::vector<uint64_t>& lengths, int ndevices = 0,
+                                       uint64_t slice_bytes = 0) {
+  if (parts.size() != lengths.size()) throw std::invalid_argument("parts/lengths size mismatch");
+  std::vector<uint32_t> crcs(parts.size());
+  if (!parts.empty())
+    sha256::batch_check(s3h_crc_batch_host(algo, parts.data(), lengths.data(), parts.size(), crcs.data(),
+                                           ndevices, slice_bytes));
+  return crcs;
+}
+
+// x-amz-content-sha256 and x-amz-checksum-crc32c / -crc32 per part from one pass over the host
+// link (s3h_sha256_crc_batch_host / s3h_sha256_crc_file_parts).
+struct Sha256Crc {
+  std::vector<uint32_t> sha256;  // 8 words per part, lib/hash layout
+  std::vector<uint32_t> crc;     // one value per part
+};
+inline Sha256Crc sha256_crc_batch(int algo, const std::vector<const uint8_t*>& parts,
+                                  const std::vector<uint64_t>& lengths, int ndevices = 0,
+                                  uint64_t slice_bytes = 0) {
+  if (parts.size() != lengths.size()) throw std::invalid_argument("parts/lengths size mismatch");
+  Sha256Crc d{std::vector<uint32_t>(8 * parts.size()), std::vector<uint32_t>(parts.size())};
+  if (!parts.empty())
+    sha256::batch_check(s3h_sha256_crc_batch_host(algo, parts.data(), lengths.data(), parts.size(),
+                                                  d.sha256.data(), d.crc.data(), ndevices, slice_bytes));
+  return d;
+}
+
+inline Sha256Crc file_part_sha256_crc(int algo, const std::string& path,
+                                      const std::vector<uint64_t>& offsets,
+                                      const std::vector<uint64_t>& lengths, int ndevices = 0) {
+  if (offsets.size() != lengths.size()) throw std::invalid_argument("offsets/lengths size mismatch");
+  Sha256Crc d{std::vector<uint32_t>(8 * offsets.size()), std::vector<uint32_t>(offsets.size())};
+  if (!offsets.empty())
+    sha256::batch_check(s3h_sha256_crc_file_parts(algo, path.c_str(), offsets.data(), lengths.data(),
+                                                  offsets.size(), d.sha256.data(), d.crc.data(), ndevices, 0));
+  return d;
+}
+
 // One message on the CPU; `seed` = a previous call's result (chunks chain like zlib's).
 inline uint32_t crc(int algo, const uint8_t* data, uint64_t length, uint32_t seed = 0) {
   if (algo != S3H_CRC32C && algo != S3H_CRC32) throw std::invalid_argument("crc: unknown checksum");

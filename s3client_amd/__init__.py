@@ -17,7 +17,8 @@ from .hashing import (Plan, device_count, digests_to_text, generate_parts, hash_
                       route_device_rates, route_refresh_calls, route_scale, host_plan,
                       device_power_cap, pci_power_cap,
                       CrcPlan, crc_batch_device, crc_verify_batch_device, crc, crc_combine,
-                      crc_object, checksum_text)
+                      crc_object, checksum_text, crc_batch_host, sha256_crc_batch_host,
+                      sha256_crc_file_parts)
 from .upload import upload_parts_geometry, UploadPart
 from ._native import S3HashError, LIB_PATH
 
@@ -34,5 +35,6 @@ __all__ = ["BufferParts", "Plan", "device_count", "digests_to_text", "generate_p
            "route_rates", "route_choose", "route_device_rates", "route_refresh_calls",
            "route_scale", "host_plan", "device_power_cap", "pci_power_cap",
            "CrcPlan", "crc_batch_device", "crc_verify_batch_device", "crc", "crc_combine",
-           "crc_object", "checksum_text",
+           "crc_object", "checksum_text", "crc_batch_host", "sha256_crc_batch_host",
+           "sha256_crc_file_parts",
            "upload_parts_geometry", "UploadPart", "S3HashError", "LIB_PATH"]

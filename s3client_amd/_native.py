@@ -52,6 +52,9 @@ C_ABI_SYMBOLS = (
     "s3h_crc_plan_create", "s3h_crc_plan_launch", "s3h_crc_plan_info", "s3h_crc_plan_destroy",
     "s3h_crc_batch_device", "s3h_crc_verify_batch_device", "s3h_cpu_crc", "s3h_crc_combine",
     "s3h_crc_object", "s3h_checksum_text",
+    # ranged CRC launches, SHA-256 + CRC of host-resident parts in one pass
+    "s3h_crc_plan_launch_range", "s3h_crc_batch_host", "s3h_sha256_crc_batch_host",
+    "s3h_sha256_crc_file_parts",
 )
 CRC32C, CRC32 = 0, 1
 CRC_IDS = {"crc32c": CRC32C, "crc32": CRC32}
@@ -327,6 +330,19 @@ def lib() -> ctypes.CDLL:
             L.s3h_crc_plan_launch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                               ctypes.c_void_p]
             L.s3h_crc_plan_info.argtypes = [ctypes.c_void_p, u64p, u64p, u64p, u32p]
+            L.s3h_crc_plan_launch_range.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
+                                                    ctypes.c_void_p, ctypes.c_uint64,
+                                                    ctypes.c_uint64, ctypes.c_uint64,
+                                                    ctypes.c_void_p]
+            L.s3h_crc_batch_host.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), u64p,
+                                             ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int,
+                                             ctypes.c_uint64]
+            L.s3h_sha256_crc_batch_host.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),
+                                                    u64p, ctypes.c_uint64, ctypes.c_void_p,
+                                                    ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64]
+            L.s3h_sha256_crc_file_parts.argtypes = [ctypes.c_int, ctypes.c_char_p, u64p, u64p,
+                                                    ctypes.c_uint64, ctypes.c_void_p,
+                                                    ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64]
             L.s3h_crc_plan_destroy.argtypes = [ctypes.c_void_p]
             L.s3h_crc_batch_device.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, u64p,
                                                u64p, ctypes.c_uint64, ctypes.c_void_p,

@@ -1,28 +1,14 @@
-// crc.cpp -- CRC-32C / CRC-32 of device-resident parts: the plan (segment table built on the
-// host and uploaded once, per-polynomial lookup tables, the partials buffer the two launches
-// hand segment values through) and the s3h_crc_* entry points of include/s3hash.h.  The
+// crc.cpp -- CRC-32C / CRC-32 of device-resident parts: the plan (per-part records and, for
+// whole-part launches, a segment table, built on the host and uploaded once; per-polynomial
+// lookup tables; the partials buffer the two stages hand segment values through; the per-part
+// running values of ranged launches) and the s3h_crc_* entry points of include/s3hash.h.  The
+// host pipeline (host_path.cpp) reuses plans through crc_plan_alloc / _reserve / _refill.  The
 // arithmetic is crc_math.hpp (shared with the kernels); the CPU functions are cpu/lib_crc.cpp.
 #include <algorithm>
 #include <vector>
 
 #include "crc_math.hpp"
 #include "internal.hpp"
-
-struct s3h_crc_plan_s {
-  int device = 0;
-  int crc = S3H_CRC32C;
-  uint32_t poly = 0;
-  uint64_t n = 0;
-  uint64_t nseg = 0;
-  uint32_t log2_segment = 0;
-  uint32_t grid = 0;               // workgroups of the segment launch
-  s3h::CrcSeg* d_segs = nullptr;
-  s3h::CrcPart* d_parts = nullptr;
-  uint32_t* d_tables = nullptr;
-  // One raw value per segment, written by stage 1 and read by stage 2 of the same launch:
-  // plan-owned, so one plan runs on one stream at a time (include/s3hash.h).
-  uint32_t* d_partials = nullptr;
-};
 
 using namespace s3h::host;
 namespace gf = s3h::crc;
@@ -52,50 +38,69 @@ int check_crc_args(int crc, const void* a, const void* b, uint64_t n) {
   return S3H_OK;
 }
 
+uint32_t pick_log2_segment(const uint64_t* lengths, uint64_t n) {
+  uint32_t log2s = kLog2SegMax;
+  while (log2s > kLog2SegMin && count_segments(lengths, n, log2s) < kMinSegments) --log2s;
+  return log2s;
+}
+
+uint32_t seg_grid(const s3h_crc_plan_s* P, uint64_t waves) {
+  const uint64_t wgs = (waves + kSegWaves - 1) / kSegWaves;
+  return uint32_t(std::min<uint64_t>(std::max<uint64_t>(wgs, 1), uint64_t(std::max(P->cus, 1)) * kWgsPerCu));
+}
+
+// The plan's geometry for these parts and its per-part records (n entries each).
+void fill_records(s3h_crc_plan_s* P, const uint64_t* offsets, const uint64_t* lengths, uint64_t n,
+                  s3h::CrcPart* parts, uint64_t* offs) {
+  P->n = n;
+  P->log2_segment = pick_log2_segment(lengths, n);
+  P->longest = 0;
+  P->range_end = 0;
+  uint64_t k = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    parts[i] = {k, lengths[i]};
+    offs[i] = offsets[i];
+    k += (lengths[i] + (uint64_t(1) << P->log2_segment) - 1) >> P->log2_segment;
+    P->longest = std::max(P->longest, lengths[i]);
+  }
+  P->nseg = k;
+  P->grid = seg_grid(P, k);
+}
+
+template <class T>
+hipError_t regrow(T** p, uint64_t count) {
+  if (*p) (void)hipFree(*p);
+  *p = nullptr;
+  return hipMalloc(reinterpret_cast<void**>(p), std::max<uint64_t>(count, 1) * sizeof(T));
+}
+
 int crc_plan_build(int device, int crc, const uint64_t* offsets, const uint64_t* lengths,
                    uint64_t n, s3h_crc_plan_s** out) {
   *out = nullptr;
   if (int rc = check_crc_args(crc, offsets, lengths, n)) return rc;
-  if (int rc = check_device(device)) return rc;
-  auto* P = new s3h_crc_plan_s;
+  s3h_crc_plan_s* P = nullptr;
+  if (int rc = crc_plan_alloc(device, crc, &P)) return rc;
   struct Guard {
     s3h_crc_plan_s* P;
     ~Guard() { if (P) s3h_crc_plan_destroy(P); }
   } guard{P};
-  P->device = device;
-  P->crc = crc;
-  P->poly = crc == S3H_CRC32C ? gf::kPolyCrc32c : gf::kPolyCrc32;
-  P->n = n;
-  P->log2_segment = kLog2SegMax;
-  while (P->log2_segment > kLog2SegMin && count_segments(lengths, n, P->log2_segment) < kMinSegments)
-    --P->log2_segment;
-  P->nseg = count_segments(lengths, n, P->log2_segment);
-  const uint64_t S = uint64_t(1) << P->log2_segment;
-
   std::vector<s3h::CrcPart> parts(n);
+  std::vector<uint64_t> offs(n);
+  fill_records(P, offsets, lengths, n, parts.data(), offs.data());
+  const uint64_t S = uint64_t(1) << P->log2_segment;
   std::vector<s3h::CrcSeg> segs(P->nseg);
   uint64_t k = 0;
-  for (uint64_t i = 0; i < n; ++i) {
-    parts[i] = {k, lengths[i]};
+  for (uint64_t i = 0; i < n; ++i)
     for (uint64_t done = 0; done < lengths[i]; done += S)
       segs[k++] = {offsets[i] + done, uint32_t(std::min(S, lengths[i] - done)), 0};
-  }
-  std::vector<uint32_t> tables(gf::kTableWords);
-  gf::build_device_tables(P->poly, tables.data());
 
-  const int cus = std::max(device_cus(device), 1);
-  const uint64_t wgs = (P->nseg + kSegWaves - 1) / kSegWaves;
-  P->grid = uint32_t(std::min<uint64_t>(std::max<uint64_t>(wgs, 1), uint64_t(cus) * kWgsPerCu));
-
+  if (int rc = crc_plan_reserve(P, n, P->nseg)) return rc;
   DeviceGuard g(device);
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&P->d_parts), n * sizeof(s3h::CrcPart)));
   HIP_TRY(hipMalloc(reinterpret_cast<void**>(&P->d_segs), std::max<uint64_t>(P->nseg, 1) * sizeof(s3h::CrcSeg)));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&P->d_partials), std::max<uint64_t>(P->nseg, 1) * 4));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&P->d_tables), gf::kTableWords * 4));
   HIP_TRY(hipMemcpy(P->d_parts, parts.data(), n * sizeof(s3h::CrcPart), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(P->d_offs, offs.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice));
   if (P->nseg)
     HIP_TRY(hipMemcpy(P->d_segs, segs.data(), P->nseg * sizeof(s3h::CrcSeg), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(P->d_tables, tables.data(), gf::kTableWords * 4, hipMemcpyHostToDevice));
   guard.P = nullptr;
   *out = P;
   return S3H_OK;
@@ -120,10 +125,103 @@ int crc_plan_launch(s3h_crc_plan_s* P, const void* d_base, uint32_t* d_crcs, hip
   DeviceGuard g(P->device);
   (void)hipGetLastError();
   HIP_TRY(launch_crc(A, P->grid, B, s));
+  P->range_end = 0;  // the partials are shared: a ranged pass cannot go on across this launch
   return S3H_OK;
 }
 
 }  // namespace
+
+namespace s3h::host {
+
+int crc_plan_alloc(int device, int crc, s3h_crc_plan_s** out) {
+  *out = nullptr;
+  if (crc != S3H_CRC32C && crc != S3H_CRC32) return fail(S3H_EINVAL, "crc: unknown checksum %d", crc);
+  if (int rc = check_device(device)) return rc;
+  auto* P = new s3h_crc_plan_s;
+  struct Guard {
+    s3h_crc_plan_s* P;
+    ~Guard() { if (P) s3h_crc_plan_destroy(P); }
+  } guard{P};
+  P->device = device;
+  P->crc = crc;
+  P->poly = crc == S3H_CRC32C ? gf::kPolyCrc32c : gf::kPolyCrc32;
+  P->cus = device_cus(device);
+  std::vector<uint32_t> tables(gf::kTableWords);
+  gf::build_device_tables(P->poly, tables.data());
+  DeviceGuard g(device);
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&P->d_tables), gf::kTableWords * 4));
+  HIP_TRY(hipMemcpy(P->d_tables, tables.data(), gf::kTableWords * 4, hipMemcpyHostToDevice));
+  guard.P = nullptr;
+  *out = P;
+  return S3H_OK;
+}
+
+uint64_t crc_max_segments(const uint64_t* lengths, uint64_t n) {
+  return count_segments(lengths, n, kLog2SegMin);
+}
+
+int crc_plan_reserve(s3h_crc_plan_s* P, uint64_t parts, uint64_t segments) {
+  DeviceGuard g(P->device);
+  if (P->cap < parts) {
+    P->cap = 0;
+    HIP_TRY(regrow(&P->d_parts, parts));
+    HIP_TRY(regrow(&P->d_offs, parts));
+    HIP_TRY(regrow(&P->d_state, parts));
+    P->cap = parts;
+  }
+  if (P->seg_cap < segments || !P->d_partials) {
+    P->seg_cap = 0;
+    HIP_TRY(regrow(&P->d_partials, segments));
+    P->seg_cap = segments;
+  }
+  return S3H_OK;
+}
+
+int crc_plan_refill(s3h_crc_plan_s* P, const uint64_t* offsets, const uint64_t* lengths, uint64_t n,
+                    s3h::CrcPart* h_parts, uint64_t* h_offs, hipStream_t s) {
+  if (n == 0 || n > P->cap) return fail(S3H_EINVAL, "crc refill: %llu parts, room for %llu",
+                                        (unsigned long long)n, (unsigned long long)P->cap);
+  fill_records(P, offsets, lengths, n, h_parts, h_offs);
+  if (P->nseg > P->seg_cap) return fail(S3H_EINVAL, "crc refill: %llu segments, room for %llu",
+                                        (unsigned long long)P->nseg, (unsigned long long)P->seg_cap);
+  DeviceGuard g(P->device);
+  HIP_TRY(hipMemcpyAsync(P->d_parts, h_parts, n * sizeof(s3h::CrcPart), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(P->d_offs, h_offs, n * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+  return S3H_OK;
+}
+
+// No allocation, no synchronisation, no upload: two kernel launches.
+int crc_plan_launch_range(s3h_crc_plan_s* P, const void* d_base, uint32_t* d_crcs, uint64_t begin,
+                          uint64_t end, uint64_t origin, hipStream_t s) {
+  if (begin >= end || origin > begin)
+    return fail(S3H_EINVAL, "crc range: need byte_origin <= byte_begin < byte_end (%llu, %llu, %llu)",
+                (unsigned long long)origin, (unsigned long long)begin, (unsigned long long)end);
+  if (begin != 0 && begin != P->range_end)
+    return fail(S3H_EINVAL, "crc range: byte_begin %llu does not continue the previous range (ended at %llu)",
+                (unsigned long long)begin, (unsigned long long)P->range_end);
+  s3h::CrcRangeArgs A;
+  A.base = static_cast<const uint8_t*>(d_base);
+  A.parts = P->d_parts;
+  A.offs = P->d_offs;
+  A.tables = P->d_tables;
+  A.partials = P->d_partials;
+  A.state = P->d_state;
+  A.crcs = d_crcs;
+  A.n = P->n;
+  A.begin = begin;
+  A.end = end;
+  A.origin = origin;
+  A.poly = P->poly;
+  A.x_segment = gf::xpow8(uint64_t(1) << P->log2_segment, P->poly);
+  A.log2_segment = P->log2_segment;
+  DeviceGuard g(P->device);
+  (void)hipGetLastError();
+  HIP_TRY(launch_crc_range(A, seg_grid(P, P->n * gf::range_pieces(begin, end, P->log2_segment)), s));
+  P->range_end = end;
+  return S3H_OK;
+}
+
+}  // namespace s3h::host
 
 extern "C" {
 
@@ -136,6 +234,14 @@ int s3h_crc_plan_create(int device, int crc, const uint64_t* offsets, const uint
 int s3h_crc_plan_launch(s3h_crc_plan_t P, const void* d_base, uint32_t* d_crcs, void* stream) {
   if (!P || !d_base || !d_crcs) return fail(S3H_EINVAL, "crc launch: null argument");
   return crc_plan_launch(P, d_base, d_crcs, static_cast<hipStream_t>(stream));
+}
+
+int s3h_crc_plan_launch_range(s3h_crc_plan_t P, const void* d_base, uint32_t* d_crcs,
+                              uint64_t byte_begin, uint64_t byte_end, uint64_t byte_origin,
+                              void* stream) {
+  if (!P || !d_base || !d_crcs) return fail(S3H_EINVAL, "crc range launch: null argument");
+  return crc_plan_launch_range(P, d_base, d_crcs, byte_begin, byte_end, byte_origin,
+                               static_cast<hipStream_t>(stream));
 }
 
 int s3h_crc_plan_info(s3h_crc_plan_t P, uint64_t* n, uint64_t* segments, uint64_t* segment_bytes,
@@ -155,6 +261,8 @@ int s3h_crc_plan_destroy(s3h_crc_plan_t P) {
   (void)hipFree(P->d_parts);
   (void)hipFree(P->d_tables);
   (void)hipFree(P->d_partials);
+  (void)hipFree(P->d_offs);
+  (void)hipFree(P->d_state);
   delete P;
   return S3H_OK;
 }

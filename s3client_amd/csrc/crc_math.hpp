@@ -186,4 +186,68 @@ S3H_CRC_HD SegGeom seg_geom(uint64_t addr, uint64_t len) {
   return g;
 }
 
+// ---------------------------------------------------------------- ranged (resumable) launches
+// A ranged launch covers bytes [begin, end) of every part.  Its pieces are cut on the plan's
+// segment grid (S = 2^log2s bytes, counted from each part's byte 0): piece k of a part of `len`
+// bytes is [k * S, (k + 1) * S) & [begin, end) & [0, len).  Stage 1 runs one wave per
+// (part, k) with k in [range_first_piece, + range_pieces) and leaves piece k's raw value in the
+// part's k-th slot of the partials buffer; stage 2 folds the part's pieces into its running
+// value.  The kernels (crc_range_pieces_kernel, crc_range_parts_kernel) and the host model
+// (tests/cpp/crc_range_model.cpp) both call these functions.
+
+S3H_CRC_HD uint64_t range_first_piece(uint64_t begin, uint32_t log2s) { return begin >> log2s; }
+// pieces per part of a launch (begin < end)
+S3H_CRC_HD uint64_t range_pieces(uint64_t begin, uint64_t end, uint32_t log2s) {
+  return ((end - 1) >> log2s) - (begin >> log2s) + 1;
+}
+
+struct Piece {
+  uint64_t lo, hi;  // bytes [lo, hi) of the part; empty when lo >= hi
+};
+S3H_CRC_HD Piece piece_of(uint64_t k, uint32_t log2s, uint64_t begin, uint64_t end, uint64_t len) {
+  const uint64_t a = k << log2s, b = a + (uint64_t(1) << log2s), e = end < len ? end : len;
+  Piece p;
+  p.lo = a > begin ? a : begin;
+  p.hi = b < e ? b : e;
+  return p;
+}
+
+// What stage 2 does for one part of `len` bytes in a launch over [begin, end).
+struct PartRange {
+  uint64_t bytes;   // m: bytes of the part inside the range (0: the part is not touched, unless
+                    // it is empty and begin == 0, when its CRC is written)
+  uint64_t first;   // k of the part's first non-empty piece
+  uint64_t front;   // pieces in front of the last one; all but the first of them hold S bytes,
+                    // and the first folds like a whole one (its missing front is leading zeros)
+  uint64_t tail;    // bytes of the last piece (1..S)
+  bool emits;       // the range holds the part's last byte (or the part is empty, begin == 0)
+};
+S3H_CRC_HD PartRange part_range(uint64_t len, uint64_t begin, uint64_t end, uint32_t log2s) {
+  PartRange r;
+  const uint64_t e = end < len ? end : len;
+  r.bytes = e > begin ? e - begin : 0;
+  r.first = begin >> log2s;
+  r.front = 0;
+  r.tail = 0;
+  r.emits = r.bytes ? e == len : (len == 0 && begin == 0);
+  if (r.bytes) {
+    const uint64_t last = (e - 1) >> log2s, a = last << log2s;
+    r.front = last - r.first;
+    r.tail = e - (a > begin ? a : begin);
+  }
+  return r;
+}
+
+// The part's running raw value after a launch: `fresh` is the raw value of the range's bytes.
+// At begin == 0 the old value is ignored (a new pass starts).
+S3H_CRC_HD uint32_t range_state(uint32_t old, uint32_t fresh, uint64_t begin, uint64_t bytes, uint32_t poly) {
+  return begin == 0 ? fresh : fold(old, fresh, xpow8(bytes, poly), poly);
+}
+// finalise() of a finished part, written out: a second device caller of finalise() itself
+// stops the compiler from inlining it into crc_parts_kernel, whose machine code is pinned
+// (s3client_amd/kernel_isa_counts.json).  tests/cpp/crc_range_model.cpp checks the two agree.
+S3H_CRC_HD uint32_t range_emit(uint32_t state, uint64_t len, uint32_t poly) {
+  return ~state ^ mulmod(0xFFFFFFFFu, xpow8(len, poly), poly);
+}
+
 }  // namespace s3h::crc

@@ -7,6 +7,9 @@
 // bytes, one copy stream and one hash stream per algorithm; slice k of every part is copied
 // while slice k-1 is hashed by a resumable launch (sha256_stream semantics, lib/hash/
 // sha256.cpp:84-144).  Many small parts go in groups of whole parts instead (run_host_groups).
+// An algorithm is SHA-256, MD5 or a CRC (host_limits.hpp is_crc): a CRC's "plan" is a CRC plan
+// and its resumable launch s3h_crc_plan_launch_range's, so SHA-256 and the x-amz-checksum-crc32c
+// / -crc32 value of a part come out of one pass over the host link.
 #include <fcntl.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -82,6 +85,13 @@ struct HostCtx {
   s3h_plan_s* gplan[2][kHostMaxAlgo] = {};
   uint8_t* gpin = nullptr;
   uint64_t gpin_bytes = 0;
+  // A CRC in algorithm slot a: its plan (records, tables, partials, running values) in place of
+  // plan[a] / gplan[q][a], cached and grown like them, and the pinned staging of the records
+  // (set 0: the slice pipeline and group set 0, set 1: group set 1)
+  s3h_crc_plan_s* crc[kHostMaxAlgo] = {};
+  s3h_crc_plan_s* gcrc[2][kHostMaxAlgo] = {};
+  uint8_t* crc_pin = nullptr;
+  uint64_t crc_pin_bytes = 0;
 
   hipError_t ensure_streams() {
     hipError_t e = hipSuccess;
@@ -145,6 +155,29 @@ struct HostCtx {
     P = nullptr;
     return plan_alloc(device, algo, std::max<uint64_t>(n, 1024), &P);
   }
+  // the CRC plan of slot a (group set q, or the slice pipeline's) for `algo`, with room for n
+  // parts and `segs` segment values -- the only place a CRC allocates
+  int ensure_crc(s3h_crc_plan_s** P, int algo, uint64_t n, uint64_t segs) {
+    if (*P && (*P)->crc != crc_of(algo)) {
+      s3h_crc_plan_destroy(*P);
+      *P = nullptr;
+    }
+    if (!*P)
+      if (int rc = crc_plan_alloc(device, crc_of(algo), P)) return rc;
+    return crc_plan_reserve(*P, std::max<uint64_t>(n, 1024), std::max<uint64_t>(segs, 1024));
+  }
+  static constexpr uint64_t kCrcRec = sizeof(s3h::CrcPart) + sizeof(uint64_t);
+  uint64_t crc_pin_cap() const { return crc_pin_bytes / (2 * kHostMaxAlgo * kCrcRec); }
+  hipError_t ensure_crc_pin(uint64_t n) {
+    return grow_pinned(&crc_pin, &crc_pin_bytes, 2 * kHostMaxAlgo * std::max<uint64_t>(n, 1024) * kCrcRec);
+  }
+  s3h::CrcPart* crc_parts(int q, int a) {
+    return reinterpret_cast<s3h::CrcPart*>(crc_pin) + uint64_t(q * kHostMaxAlgo + a) * crc_pin_cap();
+  }
+  uint64_t* crc_offs(int q, int a) {
+    return reinterpret_cast<uint64_t*>(reinterpret_cast<s3h::CrcPart*>(crc_pin) + 2 * kHostMaxAlgo * crc_pin_cap()) +
+           uint64_t(q * kHostMaxAlgo + a) * crc_pin_cap();
+  }
   uint64_t gpin_cap() const { return gpin_bytes / (2 * kHostMaxAlgo * (sizeof(s3h::Slot) + 4)); }
   hipError_t ensure_gpin(uint64_t n) {
     return grow_pinned(&gpin, &gpin_bytes, 2 * kHostMaxAlgo * std::max<uint64_t>(n, 1024) * (sizeof(s3h::Slot) + 4));
@@ -197,6 +230,10 @@ struct HostCtx {
     for (auto& row : gplan)
       for (s3h_plan_s* p : row)
         if (p) s3h_plan_destroy(p);
+    for (s3h_crc_plan_s* p : crc) s3h_crc_plan_destroy(p);
+    for (auto& row : gcrc)
+      for (s3h_crc_plan_s* p : row) s3h_crc_plan_destroy(p);
+    pinned_free(crc_pin);
     if (ring) (void)hipFree(ring);
     pinned_free(stage);
     pinned_free(pin);
@@ -381,8 +418,15 @@ int run_host_groups(HostCtx& C, const HostShard& sh, const int* algos, int nalgo
   bool chunk_used[kHostRing] = {};
   uint64_t chunk_next = 0;
   HIP_TRY(C.ensure_gpin(maxparts));
+  bool any_crc = false;
+  for (int a = 0; a < nalgo; ++a) any_crc = any_crc || is_crc(algos[a]);
+  if (any_crc) HIP_TRY(C.ensure_crc_pin(maxparts));
   for (int q = 0; q < 2; ++q)
     for (int a = 0; a < nalgo; ++a) {
+      if (is_crc(algos[a])) {  // a group's segments at any segment size: <= parts + bytes / 16 KiB
+        if (int rc = C.ensure_crc(&C.gcrc[q][a], algos[a], maxparts, maxparts + (maxb >> 14))) return rc;
+        continue;
+      }
       if (int rc = C.ensure_gplan(q, a, algos[a], maxparts)) return rc;
       HIP_TRY(hipMemsetAsync(C.gplan[q][a]->d_err, 0, sizeof(uint32_t), C.copy_s));
     }
@@ -410,8 +454,11 @@ int run_host_groups(HostCtx& C, const HostShard& sh, const int* algos, int nalgo
     for (uint64_t t = 0; t < ng; ++t)
       offs[t] = direct ? (lens[j0 + t] ? uint64_t(parts[sh.parts[j0 + t]] - base) : 0) : poff[j0 + t];
     for (int a = 0; a < nalgo; ++a)
-      if (int rc = plan_geometry(C.gplan[q][a], offs.data(), lens.data() + j0, ng, S3H_KERNEL_AUTO,
-                                 C.gslots(q, a), C.gorder(q, a), C.copy_s))
+      if (int rc = is_crc(algos[a])
+                       ? crc_plan_refill(C.gcrc[q][a], offs.data(), lens.data() + j0, ng,
+                                         C.crc_parts(q, a), C.crc_offs(q, a), C.copy_s)
+                       : plan_geometry(C.gplan[q][a], offs.data(), lens.data() + j0, ng, S3H_KERNEL_AUTO,
+                                       C.gslots(q, a), C.gorder(q, a), C.copy_s))
         return rc;
     if (direct) {
       if (span) HIP_TRY(hipMemcpyAsync(dgrp, base, span, hipMemcpyHostToDevice, C.copy_s));
@@ -439,9 +486,15 @@ int run_host_groups(HostCtx& C, const HostShard& sh, const int* algos, int nalgo
     for (int a = 0; a < nalgo; ++a) {
       s3h_plan_s* P = C.gplan[q][a];
       HIP_TRY(hipStreamWaitEvent(C.hash_s[a], C.copied[q], 0));
-      if (int rc = plan_launch(P, dgrp, C.d_dig[a] + j0 * digest_words(algos[a]), 0, P->max_blocks, 0,
-                               C.hash_s[a], false))
+      if (is_crc(algos[a])) {  // whole parts: one ranged launch from byte 0 to the longest part's end
+        s3h_crc_plan_s* R = C.gcrc[q][a];
+        if (int rc = crc_plan_launch_range(R, dgrp, C.d_dig[a] + j0, 0, std::max<uint64_t>(R->longest, 1), 0,
+                                           C.hash_s[a]))
+          return rc;
+      } else if (int rc = plan_launch(P, dgrp, C.d_dig[a] + j0 * digest_words(algos[a]), 0, P->max_blocks, 0,
+                                      C.hash_s[a], false)) {
         return rc;
+      }
       HIP_TRY(hipEventRecord(C.hashed[q][a], C.hash_s[a]));
     }
   }
@@ -455,7 +508,7 @@ int run_host_groups(HostCtx& C, const HostShard& sh, const int* algos, int nalgo
       rc = fail(S3H_EHIP, "D2H digests: %s", hipGetErrorString(e));
       break;
     }
-    for (int q = 0; q < 2 && rc == S3H_OK; ++q) rc = plan_check(C.gplan[q][a], C.hash_s[a]);
+    for (int q = 0; q < 2 && rc == S3H_OK && !is_crc(algos[a]); ++q) rc = plan_check(C.gplan[q][a], C.hash_s[a]);
     if (rc) break;
     for (uint64_t j = 0; j < n; ++j) std::memcpy(digests[a] + dw * sh.parts[j], &local[dw * j], dw * 4);
   }
@@ -555,6 +608,19 @@ int run_host_shard(HostCtx& C, const HostShard& sh, const int* algos, int nalgo,
   HIP_TRY(C.ensure_pin(n));
   uint64_t max_blocks = 0;
   for (int a = 0; a < nalgo; ++a) {
+    if (is_crc(algos[a])) {
+      // records on the copy stream like the digest plans' geometry; a CRC alone runs over the
+      // longest part's bytes in 64-B blocks (one block at least: empty parts are written by
+      // the launch at byte 0), beside a digest over that digest's blocks
+      HIP_TRY(C.ensure_crc_pin(n));
+      if (int rc = C.ensure_crc(&C.crc[a], algos[a], n, crc_max_segments(lens.data(), n))) return rc;
+      HIP_TRY(C.ensure_digests(a, n * sizeof(uint32_t)));
+      if (int rc = crc_plan_refill(C.crc[a], offs.data(), lens.data(), n, C.crc_parts(0, a),
+                                   C.crc_offs(0, a), C.copy_s))
+        return rc;
+      max_blocks = std::max(max_blocks, std::max<uint64_t>(1, (longest + 63) / 64));
+      continue;
+    }
     if (int rc = C.ensure_plan(a, algos[a], n)) return rc;
     HIP_TRY(hipMemsetAsync(C.plan[a]->d_err, 0, sizeof(uint32_t), C.copy_s));  // before any launch
     HIP_TRY(C.ensure_digests(a, n * digest_words(algos[a]) * sizeof(uint32_t)));
@@ -570,8 +636,9 @@ int run_host_shard(HostCtx& C, const HostShard& sh, const int* algos, int nalgo,
   const uint64_t bps = slice / 64;  // blocks per slice
   s3h_plan_s* P0 = C.plan[0];
   s3h_plan_s* P1 = nalgo == 2 ? C.plan[1] : nullptr;
-  const bool fused = nalgo == 2 && P0->max_blocks == P1->max_blocks &&
-                     dual_mode(P0, P1, 0, bps) != kDualNone;
+  // (one grid for both digests: SHA-256 + MD5 only; a CRC always runs on its own stream)
+  const bool fused = nalgo == 2 && !is_crc(algos[0]) && !is_crc(algos[1]) &&
+                     P0->max_blocks == P1->max_blocks && dual_mode(P0, P1, 0, bps) != kDualNone;
   int rc = S3H_OK;
   uint64_t k = 0;
   const double t_setup = wall_s();
@@ -647,8 +714,13 @@ int run_host_shard(HostCtx& C, const HostShard& sh, const int* algos, int nalgo,
     for (int a = 0; a < nalgo && rc == S3H_OK && !fused; ++a) {
       if (e == hipSuccess) e = hipStreamWaitEvent(C.hash_s[a], C.copied[r], 0);
       if (e != hipSuccess) { rc = fail(S3H_EHIP, "event: %s", hipGetErrorString(e)); break; }
-      if (b0 < C.plan[a]->max_blocks)  // both pad 9 B, so equal block counts; guard anyway
+      if (is_crc(algos[a])) {  // the slice's bytes of every part; past the longest part: nothing
+        if (byte0 < std::max<uint64_t>(longest, 1))
+          rc = crc_plan_launch_range(C.crc[a], slot_base, C.d_dig[a], byte0, byte0 + sbytes, byte0,
+                                     C.hash_s[a]);
+      } else if (b0 < C.plan[a]->max_blocks) {  // both pad 9 B, so equal block counts; guard anyway
         rc = plan_launch(C.plan[a], slot_base, C.d_dig[a], b0, b0 + step, b0, C.hash_s[a], true);
+      }
       if (rc == S3H_OK) e = hipEventRecord(C.hashed[r][a], C.hash_s[a]);
     }
     if (rc == S3H_OK && e != hipSuccess) rc = fail(S3H_EHIP, "event: %s", hipGetErrorString(e));
@@ -661,7 +733,7 @@ int run_host_shard(HostCtx& C, const HostShard& sh, const int* algos, int nalgo,
     hipError_t e = hipMemcpyAsync(local.data(), C.d_dig[a], n * dw * 4, hipMemcpyDeviceToHost, hs);
     if (e == hipSuccess) e = hipStreamSynchronize(hs);
     if (e != hipSuccess) { rc = fail(S3H_EHIP, "D2H digests: %s", hipGetErrorString(e)); break; }
-    if ((rc = plan_check(C.plan[a], hs)) != S3H_OK) break;  // every slice's launch reported in
+    if (!is_crc(algos[a]) && (rc = plan_check(C.plan[a], hs)) != S3H_OK) break;  // every slice's launch reported in
     for (uint64_t j = 0; j < n; ++j)
       std::memcpy(digests[a] + dw * sh.parts[j], &local[dw * j], dw * 4);
   }
@@ -901,6 +973,44 @@ int s3h_sha256_md5_file_parts(const char* path, const uint64_t* offsets, const u
                               int ndevices, uint64_t slice_bytes) {
   static const int algos[2] = {S3H_ALGO_SHA256, S3H_ALGO_MD5};
   uint32_t* const out[2] = {sha256_digests, md5_digests};
+  return file_parts(algos, 2, path, offsets, lengths, n, out, ndevices, slice_bytes);
+}
+
+// SHA-256 + CRC / CRC alone of host-resident parts: the CRC is one more algorithm id of the
+// pipeline (host_limits.hpp).  Argument errors are reported before any device is looked for.
+static int crc_algo_id(int crc, int* id) {
+  if (crc != S3H_CRC32C && crc != S3H_CRC32) return fail(S3H_EINVAL, "crc: unknown checksum %d", crc);
+  *id = kAlgoCrcBase + crc;
+  return S3H_OK;
+}
+
+int s3h_crc_batch_host(int crc, const uint8_t* const* parts, const uint64_t* lengths, uint64_t n,
+                       uint32_t* crcs, int ndevices, uint64_t slice_bytes) {
+  int algo = 0;
+  if (int rc = crc_algo_id(crc, &algo)) return rc;
+  if (!parts || !lengths || !crcs || n == 0) return fail(S3H_EINVAL, "crc_batch_host: bad arguments");
+  return batch_host(algo, parts, lengths, n, crcs, ndevices, slice_bytes);
+}
+
+int s3h_sha256_crc_batch_host(int crc, const uint8_t* const* parts, const uint64_t* lengths,
+                              uint64_t n, uint32_t* sha256_digests, uint32_t* crcs, int ndevices,
+                              uint64_t slice_bytes) {
+  int algos[2] = {S3H_ALGO_SHA256, 0};
+  if (int rc = crc_algo_id(crc, &algos[1])) return rc;
+  if (!parts || !lengths || !sha256_digests || !crcs || n == 0)
+    return fail(S3H_EINVAL, "sha256_crc_batch_host: bad arguments");
+  uint32_t* const out[2] = {sha256_digests, crcs};
+  PartSource src;
+  src.parts = parts;
+  return batch_host(algos, 2, src, lengths, n, out, ndevices, slice_bytes);
+}
+
+int s3h_sha256_crc_file_parts(int crc, const char* path, const uint64_t* offsets,
+                              const uint64_t* lengths, uint64_t n, uint32_t* sha256_digests,
+                              uint32_t* crcs, int ndevices, uint64_t slice_bytes) {
+  int algos[2] = {S3H_ALGO_SHA256, 0};
+  if (int rc = crc_algo_id(crc, &algos[1])) return rc;
+  uint32_t* const out[2] = {sha256_digests, crcs};
   return file_parts(algos, 2, path, offsets, lengths, n, out, ndevices, slice_bytes);
 }
 

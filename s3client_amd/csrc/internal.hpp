@@ -8,7 +8,7 @@
 //   pinned.cpp    NUMA-placed pinned host memory, device placement, s3h_host_alloc / _numa
 //   host_path.cpp host-resident pipeline (slices, groups), per-device contexts, the merge queue
 //   stream.cpp    multi-object streams (s3h_stream_*)
-//   crc.cpp       CRC-32C / CRC-32 plans of device-resident parts (s3h_crc_*)
+//   crc.cpp       CRC-32C / CRC-32 plans: whole-part and ranged launches (s3h_crc_*), the host path's plans
 //   route.cpp     size-aware routing (model measurement, observed rates, routed entry points)
 //   HIP-free: status.cpp, topology.cpp, route_plan.cpp (+ copy_pool.hpp, host_queue.hpp)
 #pragma once
@@ -58,6 +58,30 @@ struct s3h_plan_s {
   // launch epoch (pacing of the MD5 waves on other workgroups); allocated on first use
   uint64_t* d_progress = nullptr;
   uint32_t progress_epoch = 0;
+};
+
+// A CRC plan (crc.cpp).  Device arrays hold `cap` parts and `seg_cap` segment values and only
+// grow (the host path reuses its plans call after call, crc_plan_reserve / crc_plan_refill).
+struct s3h_crc_plan_s {
+  int device = 0;
+  int crc = S3H_CRC32C;
+  uint32_t poly = 0;
+  uint64_t n = 0;
+  uint64_t nseg = 0;
+  uint64_t cap = 0, seg_cap = 0;
+  uint64_t longest = 0;            // longest part in bytes
+  uint32_t log2_segment = 0;
+  uint32_t grid = 0;               // workgroups of the segment launch
+  int cus = 0;
+  s3h::CrcSeg* d_segs = nullptr;   // whole-part launches only (null in the host path's plans)
+  s3h::CrcPart* d_parts = nullptr;
+  uint64_t* d_offs = nullptr;      // ranged launches: each part's byte offset
+  uint32_t* d_tables = nullptr;
+  // One raw value per segment, written by stage 1 and read by stage 2 of the same launch:
+  // plan-owned, so one plan runs on one stream at a time (include/s3hash.h).
+  uint32_t* d_partials = nullptr;
+  uint32_t* d_state = nullptr;     // ranged launches: one running raw value per part
+  uint64_t range_end = 0;          // byte_end of the last ranged launch (0: the next starts over)
 };
 
 namespace s3h::host {
@@ -131,6 +155,24 @@ hipError_t launch_generate(uint8_t* base, const s3h::GenPart* parts, uint32_t np
 // CRC stage 1 (skipped when there is no segment) then stage 2, both on `s`.
 hipError_t launch_crc(const s3h::CrcSegArgs& A, uint32_t seg_grid, const s3h::CrcPartArgs& B,
                       hipStream_t s);
+
+// Both ranged stages on `s`; `piece_grid` workgroups of kCrcSegThreads for stage 1.
+hipError_t launch_crc_range(const s3h::CrcRangeArgs& A, uint32_t piece_grid, hipStream_t s);
+
+// ------------------------------------------------------------------ CRC plans (crc.cpp)
+// The host path's use of a plan: created once per context with the tables uploaded
+// (crc_plan_alloc), grown to the call's parts and segment values (crc_plan_reserve, the only
+// step that allocates), its per-part records rewritten per call or group through pinned staging
+// on stream `s` (crc_plan_refill: h_parts / h_offs hold n entries each and stay untouched until
+// the copies have run), then ranged launches.  crc_max_segments bounds the segment values of
+// any segment size the plan may pick.
+int crc_plan_alloc(int device, int crc, s3h_crc_plan_s** out);
+uint64_t crc_max_segments(const uint64_t* lengths, uint64_t n);
+int crc_plan_reserve(s3h_crc_plan_s* P, uint64_t parts, uint64_t segments);
+int crc_plan_refill(s3h_crc_plan_s* P, const uint64_t* offsets, const uint64_t* lengths, uint64_t n,
+                    s3h::CrcPart* h_parts, uint64_t* h_offs, hipStream_t s);
+int crc_plan_launch_range(s3h_crc_plan_s* P, const void* d_base, uint32_t* d_crcs, uint64_t begin,
+                          uint64_t end, uint64_t origin, hipStream_t s);
 
 // ------------------------------------------------------------------ host memory (pinned.cpp)
 // Pinned host memory whose pages live on `node` (< 0: the runtime's hipHostMalloc).

@@ -126,6 +126,24 @@ struct CrcPartArgs {
   uint32_t x_segment;      // x^(8 * segment_bytes) mod P
   uint32_t log2_segment;
 };
+// Ranged launches (crc_range_pieces_kernel, crc_range_parts_kernel): bytes [begin, end) of every
+// part, part p's byte b at base + offs[p] + (b - origin).  Both stages derive their pieces on
+// the device (crc_math.hpp piece_of / part_range) from the per-part records, so a launch
+// uploads nothing.  Piece k of part p goes through partials[parts[p].seg0 + k].
+struct CrcRangeArgs {
+  const uint8_t* base;
+  const CrcPart* parts;
+  const uint64_t* offs;    // byte offset of each part relative to the launch's base pointer
+  const uint32_t* tables;
+  uint32_t* partials;
+  uint32_t* state;         // one running raw value (init 0) per part, kept between launches
+  uint32_t* crcs;          // written only for parts whose last byte lies in the range
+  uint64_t n;
+  uint64_t begin, end, origin;
+  uint32_t poly;
+  uint32_t x_segment;
+  uint32_t log2_segment;
+};
 constexpr int kCrcSegThreads = 512;   // 8 waves share one copy of the tables in LDS
 constexpr int kCrcPartThreads = 256;  // 4 parts per workgroup
 

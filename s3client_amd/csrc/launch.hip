@@ -112,4 +112,12 @@ hipError_t launch_crc(const s3h::CrcSegArgs& A, uint32_t seg_grid, const s3h::Cr
   return hipGetLastError();
 }
 
+hipError_t launch_crc_range(const s3h::CrcRangeArgs& A, uint32_t piece_grid, hipStream_t s) {
+  hipLaunchKernelGGL(s3h::crc_range_pieces_kernel, dim3(piece_grid), dim3(s3h::kCrcSegThreads), 0, s, A);
+  constexpr uint64_t per_wg = s3h::kCrcPartThreads / 64;
+  hipLaunchKernelGGL(s3h::crc_range_parts_kernel, dim3(uint32_t((A.n + per_wg - 1) / per_wg)),
+                     dim3(s3h::kCrcPartThreads), 0, s, A);
+  return hipGetLastError();
+}
+
 }  // namespace s3h::host

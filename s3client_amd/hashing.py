@@ -348,7 +348,8 @@ def _crc_id(algo) -> int:
 class CrcPlan:
     """Segment geometry of one batch of device-resident parts for CRC-32C / CRC-32
     (s3h_crc_plan_create).  One plan runs on one stream at a time: its segment values pass
-    through a buffer the plan owns."""
+    through a buffer the plan owns.  ``launch`` checksums whole parts; ``launch_range`` a byte
+    range of every part, resumable (after a ``launch`` the next range must begin at 0)."""
 
     def __init__(self, offsets: Sequence[int], lengths: Sequence[int], device: int = 0,
                  algo: str | int = "crc32c"):
@@ -384,6 +385,29 @@ class CrcPlan:
                                         ctypes.c_void_p(crcs.data_ptr()),
                                         ctypes.c_void_p(_stream_handle(stream))))
 
+    def launch_range(self, data, crcs, byte_begin: int, byte_end: int, byte_origin: int = 0,
+                     stream=None) -> None:
+        """Resumable form (s3h_crc_plan_launch_range): bytes [byte_begin, byte_end) of every
+        part, part p's byte b at ``data + offsets[p] + (b - byte_origin)``; the running values
+        stay in the plan.  ``crcs[p]`` is written by the launch whose range holds part p's last
+        byte (an empty part's by a launch with byte_begin == 0), no other entry is touched.
+        byte_begin is 0 (a new pass) or the previous ranged launch's byte_end."""
+        if not (data.is_cuda and crcs.is_cuda):
+            raise ValueError("data and crcs must be device tensors")
+        if crcs.numel() * crcs.element_size() < 4 * self.n:
+            raise ValueError("crcs buffer too small (need n*4 bytes)")
+        if byte_origin <= byte_begin < byte_end and self.n:  # (the library rejects the rest)
+            top = np.minimum(self.lengths, np.uint64(byte_end))
+            live = top > np.uint64(byte_begin)
+            end = int((self.offsets[live] + top[live]).max()) - byte_origin if live.any() else 0
+            if data.numel() * data.element_size() < end:
+                raise ValueError(f"data buffer ({data.numel() * data.element_size()} B) smaller "
+                                 f"than the range's extent ({end} B)")
+        check(lib().s3h_crc_plan_launch_range(self._h, ctypes.c_void_p(data.data_ptr()),
+                                              ctypes.c_void_p(crcs.data_ptr()), byte_begin,
+                                              byte_end, byte_origin,
+                                              ctypes.c_void_p(_stream_handle(stream))))
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             lib().s3h_crc_plan_destroy(self._h)
@@ -417,6 +441,46 @@ def crc_batch_device(data, offsets, lengths, algo: str | int = "crc32c", stream=
                                      offs.size, ctypes.c_void_p(out.data_ptr()),
                                      ctypes.c_void_p(_stream_handle(stream))))
     return out
+
+
+def crc_batch_host(parts: Sequence, algo: str | int = "crc32c", ndevices: int = 0,
+                   slice_bytes: int = 0) -> np.ndarray:
+    """CRC-32C / CRC-32 of host-resident parts on the GPUs (s3h_crc_batch_host): (n,) uint32."""
+    arrs, ptrs, lens = _host_parts(parts)
+    n = len(arrs)
+    out = np.zeros(n, dtype=np.uint32)
+    check(lib().s3h_crc_batch_host(_crc_id(algo), ptrs, _p64(lens), n, out.ctypes.data, ndevices,
+                                   slice_bytes))
+    return out
+
+
+def sha256_crc_batch_host(parts: Sequence, algo: str | int = "crc32c", ndevices: int = 0,
+                          slice_bytes: int = 0) -> tuple[np.ndarray, np.ndarray]:
+    """SHA-256 (n, 8) digests and CRC-32C / CRC-32 values (n,) of host-resident parts, each part
+    crossing PCIe once (s3h_sha256_crc_batch_host): x-amz-content-sha256 and
+    x-amz-checksum-crc32c / -crc32 of UploadPart."""
+    arrs, ptrs, lens = _host_parts(parts)
+    n = len(arrs)
+    sha = np.zeros((n, DIGEST_WORDS), dtype=np.uint32)
+    out = np.zeros(n, dtype=np.uint32)
+    check(lib().s3h_sha256_crc_batch_host(_crc_id(algo), ptrs, _p64(lens), n, sha.ctypes.data,
+                                          out.ctypes.data, ndevices, slice_bytes))
+    return sha, out
+
+
+def sha256_crc_file_parts(path: str, offsets, lengths, algo: str | int = "crc32c",
+                          ndevices: int = 0, slice_bytes: int = 0) -> tuple[np.ndarray, np.ndarray]:
+    """SHA-256 (n, 8) digests and CRC values (n,) of file ranges, each slice read once
+    (s3h_sha256_crc_file_parts)."""
+    offs, lens = _u64(offsets), _u64(lengths)
+    if offs.shape != lens.shape or offs.ndim != 1 or offs.size == 0:
+        raise ValueError("offsets and lengths must be 1-D, equal length and non-empty")
+    sha = np.zeros((offs.size, DIGEST_WORDS), dtype=np.uint32)
+    out = np.zeros(offs.size, dtype=np.uint32)
+    check(lib().s3h_sha256_crc_file_parts(_crc_id(algo), os.fsencode(path), _p64(offs), _p64(lens),
+                                          offs.size, sha.ctypes.data, out.ctypes.data, ndevices,
+                                          slice_bytes))
+    return sha, out
 
 
 def crc_verify_batch_device(data, offsets, lengths, expected, algo: str | int = "crc32c",

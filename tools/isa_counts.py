@@ -52,6 +52,8 @@ ALL_KERNELS = {
     # CRC-32C / CRC-32 (crc32_kernels.hip): code hashes only, no chain loop to count
     "crc_segments": "_ZN3s3h19crc_segments_kernelENS_10CrcSegArgsE",
     "crc_parts": "_ZN3s3h16crc_parts_kernelENS_11CrcPartArgsE",
+    "crc_range_pieces": "_ZN3s3h23crc_range_pieces_kernelENS_12CrcRangeArgsE",
+    "crc_range_parts": "_ZN3s3h22crc_range_parts_kernelENS_12CrcRangeArgsE",
 }
 FLAG_KERNELS = ("skew_nc2", "skews", "dual_group", "dual_group_skew", "dual_group_mixed")
 ERR_STORE = re.compile(r"^\t(global|flat|buffer)_atomic_or\b")
