@@ -34,7 +34,9 @@ extern "C" {
  * layout (8 fields) for good: new rates go to s3h_route_rates_t, which carries its size.
  * Added within version 2 (new symbols only, nothing changed): the CRC-32C / CRC-32 entry
  * points (s3h_crc_*, s3h_cpu_crc, s3h_checksum_text), then s3h_crc_plan_launch_range and the
- * host-resident forms s3h_crc_batch_host, s3h_sha256_crc_batch_host, s3h_sha256_crc_file_parts. */
+ * host-resident forms s3h_crc_batch_host, s3h_sha256_crc_batch_host, s3h_sha256_crc_file_parts,
+ * then CRC-64/NVME (s3h_crc64nvme_*, s3h_cpu_crc64nvme, s3h_checksum64_text,
+ * s3h_sha256_crc64nvme_*). */
 #define S3H_API_VERSION 2
 
 enum s3h_status {
@@ -599,6 +601,62 @@ int s3h_crc_object(int crc, const uint32_t *part_crcs, const uint64_t *lengths, 
 #define S3H_CHECKSUM_MAX 32
 int s3h_checksum_text(int crc, const uint32_t *part_crcs, uint64_t n, int composite, char *out,
                       uint64_t out_len);
+
+/* ---------------------------------------------------------------- CRC-64/NVME checksum
+ * x-amz-checksum-crc64nvme, the checksum S3 computes for every new object and current SDKs
+ * send by default: the reflected 64-bit CRC of the NVMe specification (polynomial
+ * 0xAD93D23594C93659, reflected 0x9A6C9329AC4BC9B5, init and xor-out all ones;
+ * "123456789" gives 0xAE8B14860A799888).  Values are uint64_t holding the CRC's numeric value;
+ * a part of length 0 gives 0.  S3 offers this checksum as FULL_OBJECT only: a multipart
+ * uploader sends each part's value with UploadPart and folds them with s3h_crc64nvme_object for
+ * CompleteMultipartUpload; there is no COMPOSITE form.
+ *
+ * The plan calls have the contracts of their s3h_crc_* namesakes above -- segments, one plan
+ * on one stream at a time, which ranged launch writes which d_crcs[p], byte_begin 0 or the
+ * previous byte_end -- with d_crcs holding n 64-bit words (8-byte aligned).  The enum s3h_crc
+ * entry points do not accept this checksum.  Added within API version 2. */
+typedef struct s3h_crc64nvme_plan_s *s3h_crc64nvme_plan_t;
+int s3h_crc64nvme_plan_create(int device, const uint64_t *offsets, const uint64_t *lengths,
+                              uint64_t n, s3h_crc64nvme_plan_t *plan);
+int s3h_crc64nvme_plan_launch(s3h_crc64nvme_plan_t plan, const void *d_base, uint64_t *d_crcs,
+                              void *stream);
+int s3h_crc64nvme_plan_launch_range(s3h_crc64nvme_plan_t plan, const void *d_base,
+                                    uint64_t *d_crcs, uint64_t byte_begin, uint64_t byte_end,
+                                    uint64_t byte_origin, void *stream);
+int s3h_crc64nvme_plan_info(s3h_crc64nvme_plan_t plan, uint64_t *n, uint64_t *segments,
+                            uint64_t *segment_bytes, uint32_t *grid);
+int s3h_crc64nvme_plan_destroy(s3h_crc64nvme_plan_t plan);
+/* One-shot, blocking: plan + launch + sync. */
+int s3h_crc64nvme_batch_device(int device, const void *d_base, const uint64_t *offsets,
+                               const uint64_t *lengths, uint64_t n, uint64_t *d_crcs,
+                               void *stream);
+/* As s3h_crc_verify_batch_device, against n expected 64-bit values (device).  Blocking. */
+int s3h_crc64nvme_verify_batch_device(int device, const void *d_base, const uint64_t *offsets,
+                                      const uint64_t *lengths, uint64_t n,
+                                      const uint64_t *d_expected, uint8_t *d_mismatch,
+                                      uint64_t *mismatches, void *stream);
+/* Host-resident parts, as s3h_crc_batch_host / s3h_sha256_crc_batch_host /
+ * s3h_sha256_crc_file_parts: `crcs` receives n 64-bit values in part order. */
+int s3h_crc64nvme_batch_host(const uint8_t *const *parts, const uint64_t *lengths, uint64_t n,
+                             uint64_t *crcs, int ndevices, uint64_t slice_bytes);
+int s3h_sha256_crc64nvme_batch_host(const uint8_t *const *parts, const uint64_t *lengths,
+                                    uint64_t n, uint32_t *sha256_digests, uint64_t *crcs,
+                                    int ndevices, uint64_t slice_bytes);
+int s3h_sha256_crc64nvme_file_parts(const char *path, const uint64_t *offsets,
+                                    const uint64_t *lengths, uint64_t n, uint32_t *sha256_digests,
+                                    uint64_t *crcs, int ndevices, uint64_t slice_bytes);
+/* CPU, one message (slicing-by-8 tables).  seed_crc: 0, or a previous call's result, so chunks
+ * chain.  Null data with length > 0: returns 0 and sets s3h_last_error. */
+uint64_t s3h_cpu_crc64nvme(const uint8_t *data, uint64_t length, uint64_t seed_crc);
+/* crc(A || B) from crc(A), crc(B) and |B|, without the data. */
+int s3h_crc64nvme_combine(uint64_t crc_a, uint64_t crc_b, uint64_t len_b, uint64_t *out);
+/* FULL_OBJECT checksum: the CRC of the n parts' concatenation from their CRCs and lengths. */
+int s3h_crc64nvme_object(const uint64_t *part_crcs, const uint64_t *lengths, uint64_t n,
+                         uint64_t *out);
+/* Header text of a 64-bit checksum, NUL-terminated, out_len >= S3H_CHECKSUM_MAX: the value of
+ * x-amz-checksum-crc64nvme, base64 of the CRC's 8 bytes, big-endian (12 characters) -- of a
+ * part, or of s3h_crc64nvme_object's result. */
+int s3h_checksum64_text(uint64_t crc, char *out, uint64_t out_len);
 
 /* ---------------------------------------------------------------- synthetic inputs
  * Fill part i (at d_base + offsets[i], 8-B aligned, lengths[i] bytes) with generator

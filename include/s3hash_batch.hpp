@@ -367,3 +367,85 @@ inline std::string composite_checksum_text(int algo, const std::vector<uint32_t>
 }
 
 }  // namespace crc
+
+// x-amz-checksum-crc64nvme (CRC-64/NVME): every value the CRC's number, one uint64_t per part.
+// S3 offers this checksum as FULL_OBJECT only: fold the parts' values with object_crc.
+namespace crc64 {
+
+// Parts already in device memory at d_base + offsets[i] (any alignment); n CRCs to d_crcs.
+inline void crc_batch_device(int device, const void* d_base, const std::vector<uint64_t>& offsets,
+                             const std::vector<uint64_t>& lengths, uint64_t* d_crcs,
+                             void* stream = nullptr) {
+  if (offsets.size() != lengths.size()) throw std::invalid_argument("offsets/lengths size mismatch");
+  sha256::batch_check(s3h_crc64nvme_batch_device(device, d_base, offsets.data(), lengths.data(),
+                                                 offsets.size(), d_crcs, stream));
+}
+
+// Host-resident parts on the GPUs (s3h_crc64nvme_batch_host): one CRC per part.
+inline std::vector<uint64_t> crc_batch(const std::vector<const uint8_t*>& parts,
+                                       const std::vector<uint64_t>& lengths, int ndevices = 0,
+                                       uint64_t slice_bytes = 0) {
+  if (parts.size() != lengths.size()) throw std::invalid_argument("parts/lengths size mismatch");
+  std::vector<uint64_t> crcs(parts.size());
+  if (!parts.empty())
+    sha256::batch_check(s3h_crc64nvme_batch_host(parts.data(), lengths.data(), parts.size(), crcs.data(),
+                                                 ndevices, slice_bytes));
+  return crcs;
+}
+
+// x-amz-content-sha256 and x-amz-checksum-crc64nvme per part from one pass over the host link.
+struct Sha256Crc64 {
+  std::vector<uint32_t> sha256;  // 8 words per part, lib/hash layout
+  std::vector<uint64_t> crc;     // one value per part
+};
+inline Sha256Crc64 sha256_crc_batch(const std::vector<const uint8_t*>& parts,
+                                    const std::vector<uint64_t>& lengths, int ndevices = 0,
+                                    uint64_t slice_bytes = 0) {
+  if (parts.size() != lengths.size()) throw std::invalid_argument("parts/lengths size mismatch");
+  Sha256Crc64 d{std::vector<uint32_t>(8 * parts.size()), std::vector<uint64_t>(parts.size())};
+  if (!parts.empty())
+    sha256::batch_check(s3h_sha256_crc64nvme_batch_host(parts.data(), lengths.data(), parts.size(),
+                                                        d.sha256.data(), d.crc.data(), ndevices,
+                                                        slice_bytes));
+  return d;
+}
+
+inline Sha256Crc64 file_part_sha256_crc(const std::string& path, const std::vector<uint64_t>& offsets,
+                                        const std::vector<uint64_t>& lengths, int ndevices = 0) {
+  if (offsets.size() != lengths.size()) throw std::invalid_argument("offsets/lengths size mismatch");
+  Sha256Crc64 d{std::vector<uint32_t>(8 * offsets.size()), std::vector<uint64_t>(offsets.size())};
+  if (!offsets.empty())
+    sha256::batch_check(s3h_sha256_crc64nvme_file_parts(path.c_str(), offsets.data(), lengths.data(),
+                                                        offsets.size(), d.sha256.data(), d.crc.data(),
+                                                        ndevices, 0));
+  return d;
+}
+
+// One message on the CPU; `seed` = a previous call's result (chunks chain).
+inline uint64_t crc(const uint8_t* data, uint64_t length, uint64_t seed = 0) {
+  if (!data && length) throw std::invalid_argument("crc64: null data");
+  return s3h_cpu_crc64nvme(data, length, seed);
+}
+
+inline uint64_t combine(uint64_t crc_a, uint64_t crc_b, uint64_t len_b) {
+  uint64_t out = 0;
+  sha256::batch_check(s3h_crc64nvme_combine(crc_a, crc_b, len_b, &out));
+  return out;
+}
+
+// The FULL_OBJECT checksum of a multipart upload from its parts' CRCs and lengths.
+inline uint64_t object_crc(const std::vector<uint64_t>& part_crcs, const std::vector<uint64_t>& lengths) {
+  if (part_crcs.size() != lengths.size()) throw std::invalid_argument("crcs/lengths size mismatch");
+  uint64_t out = 0;
+  sha256::batch_check(s3h_crc64nvme_object(part_crcs.data(), lengths.data(), part_crcs.size(), &out));
+  return out;
+}
+
+// Header value of one CRC (a part's, or object_crc's result): base64 of its big-endian bytes.
+inline std::string checksum_text(uint64_t value) {
+  char out[S3H_CHECKSUM_MAX];
+  sha256::batch_check(s3h_checksum64_text(value, out, sizeof out));
+  return out;
+}
+
+}  // namespace crc64

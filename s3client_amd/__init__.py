@@ -18,7 +18,10 @@ from .hashing import (Plan, device_count, digests_to_text, generate_parts, hash_
                       device_power_cap, pci_power_cap,
                       CrcPlan, crc_batch_device, crc_verify_batch_device, crc, crc_combine,
                       crc_object, checksum_text, crc_batch_host, sha256_crc_batch_host,
-                      sha256_crc_file_parts)
+                      sha256_crc_file_parts,
+                      Crc64Plan, crc64_batch_device, crc64_verify_batch_device, crc64,
+                      crc64_combine, crc64_object, checksum64_text, crc64_batch_host,
+                      sha256_crc64_batch_host, sha256_crc64_file_parts)
 from .upload import upload_parts_geometry, UploadPart
 from ._native import S3HashError, LIB_PATH
 
@@ -37,4 +40,7 @@ __all__ = ["BufferParts", "Plan", "device_count", "digests_to_text", "generate_p
            "CrcPlan", "crc_batch_device", "crc_verify_batch_device", "crc", "crc_combine",
            "crc_object", "checksum_text", "crc_batch_host", "sha256_crc_batch_host",
            "sha256_crc_file_parts",
+           "Crc64Plan", "crc64_batch_device", "crc64_verify_batch_device", "crc64",
+           "crc64_combine", "crc64_object", "checksum64_text", "crc64_batch_host",
+           "sha256_crc64_batch_host", "sha256_crc64_file_parts",
            "upload_parts_geometry", "UploadPart", "S3HashError", "LIB_PATH"]

@@ -55,8 +55,15 @@ C_ABI_SYMBOLS = (
     # ranged CRC launches, SHA-256 + CRC of host-resident parts in one pass
     "s3h_crc_plan_launch_range", "s3h_crc_batch_host", "s3h_sha256_crc_batch_host",
     "s3h_sha256_crc_file_parts",
+    # CRC-64/NVME
+    "s3h_crc64nvme_plan_create", "s3h_crc64nvme_plan_launch", "s3h_crc64nvme_plan_launch_range",
+    "s3h_crc64nvme_plan_info", "s3h_crc64nvme_plan_destroy", "s3h_crc64nvme_batch_device",
+    "s3h_crc64nvme_verify_batch_device", "s3h_cpu_crc64nvme", "s3h_crc64nvme_combine",
+    "s3h_crc64nvme_object", "s3h_checksum64_text", "s3h_crc64nvme_batch_host",
+    "s3h_sha256_crc64nvme_batch_host", "s3h_sha256_crc64nvme_file_parts",
 )
 CRC32C, CRC32 = 0, 1
+CRC64NVME = "crc64nvme"  # not an enum s3h_crc: the checksum has entry points of its own
 CRC_IDS = {"crc32c": CRC32C, "crc32": CRC32}
 CHECKSUM_MAX = 32
 POLICY_IDS = {"throughput": 0, "efficiency": 1, "power": 2}
@@ -344,6 +351,39 @@ def lib() -> ctypes.CDLL:
                                                     ctypes.c_uint64, ctypes.c_void_p,
                                                     ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64]
             L.s3h_crc_plan_destroy.argtypes = [ctypes.c_void_p]
+            L.s3h_crc64nvme_plan_create.argtypes = [ctypes.c_int, u64p, u64p, ctypes.c_uint64,
+                                                    ctypes.POINTER(ctypes.c_void_p)]
+            L.s3h_crc64nvme_plan_launch.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
+                                                    ctypes.c_void_p, ctypes.c_void_p]
+            L.s3h_crc64nvme_plan_launch_range.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
+                                                          ctypes.c_void_p, ctypes.c_uint64,
+                                                          ctypes.c_uint64, ctypes.c_uint64,
+                                                          ctypes.c_void_p]
+            L.s3h_crc64nvme_plan_info.argtypes = [ctypes.c_void_p, u64p, u64p, u64p, u32p]
+            L.s3h_crc64nvme_plan_destroy.argtypes = [ctypes.c_void_p]
+            L.s3h_crc64nvme_batch_device.argtypes = [ctypes.c_int, ctypes.c_void_p, u64p, u64p,
+                                                     ctypes.c_uint64, ctypes.c_void_p,
+                                                     ctypes.c_void_p]
+            L.s3h_crc64nvme_verify_batch_device.argtypes = [ctypes.c_int, ctypes.c_void_p, u64p,
+                                                            u64p, ctypes.c_uint64, ctypes.c_void_p,
+                                                            ctypes.c_void_p, u64p, ctypes.c_void_p]
+            L.s3h_crc64nvme_batch_host.argtypes = [ctypes.POINTER(ctypes.c_void_p), u64p,
+                                                   ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int,
+                                                   ctypes.c_uint64]
+            L.s3h_sha256_crc64nvme_batch_host.argtypes = [ctypes.POINTER(ctypes.c_void_p), u64p,
+                                                          ctypes.c_uint64, ctypes.c_void_p,
+                                                          ctypes.c_void_p, ctypes.c_int,
+                                                          ctypes.c_uint64]
+            L.s3h_sha256_crc64nvme_file_parts.argtypes = [ctypes.c_char_p, u64p, u64p,
+                                                          ctypes.c_uint64, ctypes.c_void_p,
+                                                          ctypes.c_void_p, ctypes.c_int,
+                                                          ctypes.c_uint64]
+            L.s3h_cpu_crc64nvme.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64]
+            L.s3h_cpu_crc64nvme.restype = ctypes.c_uint64
+            L.s3h_crc64nvme_combine.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
+                                                u64p]
+            L.s3h_crc64nvme_object.argtypes = [ctypes.c_void_p, u64p, ctypes.c_uint64, u64p]
+            L.s3h_checksum64_text.argtypes = [ctypes.c_uint64, ctypes.c_char_p, ctypes.c_uint64]
             L.s3h_crc_batch_device.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, u64p,
                                                u64p, ctypes.c_uint64, ctypes.c_void_p,
                                                ctypes.c_void_p]

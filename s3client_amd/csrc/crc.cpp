@@ -1,17 +1,21 @@
-// crc.cpp -- CRC-32C / CRC-32 of device-resident parts: the plan (per-part records and, for
+// crc.cpp -- CRC-32C / CRC-32 / CRC-64/NVME of device-resident parts: the plan (per-part records and, for
 // whole-part launches, a segment table, built on the host and uploaded once; per-polynomial
 // lookup tables; the partials buffer the two stages hand segment values through; the per-part
-// running values of ranged launches) and the s3h_crc_* entry points of include/s3hash.h.  The
+// running values of ranged launches) and the s3h_crc_* / s3h_crc64nvme_* entry points of
+// include/s3hash.h.  A 64-bit plan is the same plan with two words per value (words == 2) and
+// the kernels of crc64_kernels.hip; everything about geometry is shared.  The
 // host pipeline (host_path.cpp) reuses plans through crc_plan_alloc / _reserve / _refill.  The
 // arithmetic is crc_math.hpp (shared with the kernels); the CPU functions are cpu/lib_crc.cpp.
 #include <algorithm>
 #include <vector>
 
+#include "crc64_math.hpp"
 #include "crc_math.hpp"
 #include "internal.hpp"
 
 using namespace s3h::host;
 namespace gf = s3h::crc;
+namespace gf64 = s3h::crc64;
 
 namespace {
 
@@ -23,6 +27,8 @@ constexpr uint32_t kLog2SegMin = 14, kLog2SegMax = 18;
 constexpr uint64_t kMinSegments = 8192;
 constexpr uint32_t kSegWaves = s3h::kCrcSegThreads / 64;
 constexpr uint32_t kWgsPerCu = 4;  // 4 x 20.5 KiB of LDS, 32 waves: a full CU
+static_assert(s3h::kCrc64SegThreads == s3h::kCrcSegThreads, "one grid rule for both widths");
+constexpr uint32_t kWgsPerCu64 = 3;  // 3 x 48.6 KiB of LDS, 24 waves (6 per SIMD)
 
 uint64_t count_segments(const uint64_t* lengths, uint64_t n, uint32_t log2s) {
   uint64_t s = 0;
@@ -30,12 +36,17 @@ uint64_t count_segments(const uint64_t* lengths, uint64_t n, uint32_t log2s) {
   return s;
 }
 
-int check_crc_args(int crc, const void* a, const void* b, uint64_t n) {
-  if (crc != S3H_CRC32C && crc != S3H_CRC32) return fail(S3H_EINVAL, "crc: unknown checksum %d", crc);
+int check_batch_args(const void* a, const void* b, uint64_t n) {
   if (!a || !b) return fail(S3H_EINVAL, "crc: null offsets or lengths");
   if (n == 0 || n > kMaxParts)
     return fail(S3H_EINVAL, "crc: need 0 < n <= 2^31 (n=%llu)", (unsigned long long)n);
   return S3H_OK;
+}
+
+// the 32-bit entry points: enum s3h_crc only
+int check_crc_args(int crc, const void* a, const void* b, uint64_t n) {
+  if (crc != S3H_CRC32C && crc != S3H_CRC32) return fail(S3H_EINVAL, "crc: unknown checksum %d", crc);
+  return check_batch_args(a, b, n);
 }
 
 uint32_t pick_log2_segment(const uint64_t* lengths, uint64_t n) {
@@ -46,7 +57,8 @@ uint32_t pick_log2_segment(const uint64_t* lengths, uint64_t n) {
 
 uint32_t seg_grid(const s3h_crc_plan_s* P, uint64_t waves) {
   const uint64_t wgs = (waves + kSegWaves - 1) / kSegWaves;
-  return uint32_t(std::min<uint64_t>(std::max<uint64_t>(wgs, 1), uint64_t(std::max(P->cus, 1)) * kWgsPerCu));
+  const uint32_t per_cu = P->words == 2 ? kWgsPerCu64 : kWgsPerCu;
+  return uint32_t(std::min<uint64_t>(std::max<uint64_t>(wgs, 1), uint64_t(std::max(P->cus, 1)) * per_cu));
 }
 
 // The plan's geometry for these parts and its per-part records (n entries each).
@@ -77,7 +89,7 @@ hipError_t regrow(T** p, uint64_t count) {
 int crc_plan_build(int device, int crc, const uint64_t* offsets, const uint64_t* lengths,
                    uint64_t n, s3h_crc_plan_s** out) {
   *out = nullptr;
-  if (int rc = check_crc_args(crc, offsets, lengths, n)) return rc;
+  if (int rc = check_batch_args(offsets, lengths, n)) return rc;
   s3h_crc_plan_s* P = nullptr;
   if (int rc = crc_plan_alloc(device, crc, &P)) return rc;
   struct Guard {
@@ -106,7 +118,35 @@ int crc_plan_build(int device, int crc, const uint64_t* offsets, const uint64_t*
   return S3H_OK;
 }
 
+s3h::Crc64Args crc64_args(const s3h_crc_plan_s* P, const void* d_base, void* d_crcs) {
+  s3h::Crc64Args A;
+  A.base = static_cast<const uint8_t*>(d_base);
+  A.segs = P->d_segs;
+  A.parts = P->d_parts;
+  A.offs = P->d_offs;
+  A.tables = reinterpret_cast<const uint64_t*>(P->d_tables);
+  A.partials = reinterpret_cast<uint64_t*>(P->d_partials);
+  A.state = reinterpret_cast<uint64_t*>(P->d_state);
+  A.crcs = static_cast<uint64_t*>(d_crcs);
+  A.n = P->n;
+  A.nseg = P->nseg;
+  A.begin = A.end = A.origin = 0;
+  A.poly = P->poly64;
+  A.x_segment = gf64::xpow8(uint64_t(1) << P->log2_segment, P->poly64);
+  A.log2_segment = P->log2_segment;
+  return A;
+}
+
+// d_crcs: n values of P->words words
 int crc_plan_launch(s3h_crc_plan_s* P, const void* d_base, uint32_t* d_crcs, hipStream_t s) {
+  if (P->words == 2) {
+    const s3h::Crc64Args A64 = crc64_args(P, d_base, d_crcs);
+    DeviceGuard g(P->device);
+    (void)hipGetLastError();
+    HIP_TRY(launch_crc64(A64, P->grid, s));
+    P->range_end = 0;
+    return S3H_OK;
+  }
   s3h::CrcSegArgs A;
   A.base = static_cast<const uint8_t*>(d_base);
   A.segs = P->d_segs;
@@ -135,7 +175,8 @@ namespace s3h::host {
 
 int crc_plan_alloc(int device, int crc, s3h_crc_plan_s** out) {
   *out = nullptr;
-  if (crc != S3H_CRC32C && crc != S3H_CRC32) return fail(S3H_EINVAL, "crc: unknown checksum %d", crc);
+  if (crc != S3H_CRC32C && crc != S3H_CRC32 && crc != kCrcIdCrc64Nvme)
+    return fail(S3H_EINVAL, "crc: unknown checksum %d", crc);
   if (int rc = check_device(device)) return rc;
   auto* P = new s3h_crc_plan_s;
   struct Guard {
@@ -146,6 +187,19 @@ int crc_plan_alloc(int device, int crc, s3h_crc_plan_s** out) {
   P->crc = crc;
   P->poly = crc == S3H_CRC32C ? gf::kPolyCrc32c : gf::kPolyCrc32;
   P->cus = device_cus(device);
+  if (crc == kCrcIdCrc64Nvme) {
+    P->poly = 0;
+    P->poly64 = gf64::kPolyNvme;
+    P->words = 2;
+    std::vector<uint64_t> t64(gf64::kTableWords);
+    gf64::build_device_tables(P->poly64, t64.data());
+    DeviceGuard g(device);
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&P->d_tables), gf64::kTableWords * 8));
+    HIP_TRY(hipMemcpy(P->d_tables, t64.data(), gf64::kTableWords * 8, hipMemcpyHostToDevice));
+    guard.P = nullptr;
+    *out = P;
+    return S3H_OK;
+  }
   std::vector<uint32_t> tables(gf::kTableWords);
   gf::build_device_tables(P->poly, tables.data());
   DeviceGuard g(device);
@@ -166,12 +220,12 @@ int crc_plan_reserve(s3h_crc_plan_s* P, uint64_t parts, uint64_t segments) {
     P->cap = 0;
     HIP_TRY(regrow(&P->d_parts, parts));
     HIP_TRY(regrow(&P->d_offs, parts));
-    HIP_TRY(regrow(&P->d_state, parts));
+    HIP_TRY(regrow(&P->d_state, parts * P->words));
     P->cap = parts;
   }
   if (P->seg_cap < segments || !P->d_partials) {
     P->seg_cap = 0;
-    HIP_TRY(regrow(&P->d_partials, segments));
+    HIP_TRY(regrow(&P->d_partials, segments * P->words));
     P->seg_cap = segments;
   }
   return S3H_OK;
@@ -199,6 +253,18 @@ int crc_plan_launch_range(s3h_crc_plan_s* P, const void* d_base, uint32_t* d_crc
   if (begin != 0 && begin != P->range_end)
     return fail(S3H_EINVAL, "crc range: byte_begin %llu does not continue the previous range (ended at %llu)",
                 (unsigned long long)begin, (unsigned long long)P->range_end);
+  if (P->words == 2) {
+    s3h::Crc64Args A64 = crc64_args(P, d_base, d_crcs);
+    A64.segs = nullptr;
+    A64.begin = begin;
+    A64.end = end;
+    A64.origin = origin;
+    DeviceGuard g(P->device);
+    (void)hipGetLastError();
+    HIP_TRY(launch_crc64_range(A64, seg_grid(P, P->n * gf::range_pieces(begin, end, P->log2_segment)), s));
+    P->range_end = end;
+    return S3H_OK;
+  }
   s3h::CrcRangeArgs A;
   A.base = static_cast<const uint8_t*>(d_base);
   A.parts = P->d_parts;
@@ -228,6 +294,8 @@ extern "C" {
 int s3h_crc_plan_create(int device, int crc, const uint64_t* offsets, const uint64_t* lengths,
                         uint64_t n, s3h_crc_plan_t* plan) {
   if (!plan) return fail(S3H_EINVAL, "crc: null plan out-pointer");
+  *plan = nullptr;
+  if (int rc = check_crc_args(crc, offsets, lengths, n)) return rc;
   return crc_plan_build(device, crc, offsets, lengths, n, plan);
 }
 
@@ -310,6 +378,97 @@ int s3h_crc_verify_batch_device(int device, int crc, const void* d_base, const u
     if (e == hipSuccess) e = hipMemcpyAsync(&c, d_count, 8, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) rc = fail(S3H_EHIP, "crc verify: %s", hipGetErrorString(e));
+    *mismatches = c;
+  }
+  (void)hipFreeAsync(d_crcs, s);
+  (void)hipFreeAsync(d_count, s);
+  (void)hipStreamSynchronize(s);
+  return rc;
+}
+
+// ---------------------------------------------------------------- CRC-64/NVME
+// The same plans with two words per value; d_crcs holds n 64-bit words.
+
+int s3h_crc64nvme_plan_create(int device, const uint64_t* offsets, const uint64_t* lengths, uint64_t n,
+                              s3h_crc64nvme_plan_t* plan) {
+  if (!plan) return fail(S3H_EINVAL, "crc64nvme: null plan out-pointer");
+  *plan = nullptr;
+  s3h_crc_plan_s* P = nullptr;
+  if (int rc = crc_plan_build(device, kCrcIdCrc64Nvme, offsets, lengths, n, &P)) return rc;
+  *plan = new s3h_crc64nvme_plan_s{P};
+  return S3H_OK;
+}
+
+int s3h_crc64nvme_plan_launch(s3h_crc64nvme_plan_t H, const void* d_base, uint64_t* d_crcs, void* stream) {
+  if (!H || !d_base || !d_crcs) return fail(S3H_EINVAL, "crc64nvme launch: null argument");
+  return crc_plan_launch(H->p, d_base, reinterpret_cast<uint32_t*>(d_crcs), static_cast<hipStream_t>(stream));
+}
+
+int s3h_crc64nvme_plan_launch_range(s3h_crc64nvme_plan_t H, const void* d_base, uint64_t* d_crcs,
+                                    uint64_t byte_begin, uint64_t byte_end, uint64_t byte_origin,
+                                    void* stream) {
+  if (!H || !d_base || !d_crcs) return fail(S3H_EINVAL, "crc64nvme range launch: null argument");
+  return crc_plan_launch_range(H->p, d_base, reinterpret_cast<uint32_t*>(d_crcs), byte_begin, byte_end,
+                               byte_origin, static_cast<hipStream_t>(stream));
+}
+
+int s3h_crc64nvme_plan_info(s3h_crc64nvme_plan_t H, uint64_t* n, uint64_t* segments,
+                            uint64_t* segment_bytes, uint32_t* grid) {
+  if (!H) return fail(S3H_EINVAL, "crc64nvme: null plan");
+  return s3h_crc_plan_info(H->p, n, segments, segment_bytes, grid);
+}
+
+int s3h_crc64nvme_plan_destroy(s3h_crc64nvme_plan_t H) {
+  if (!H) return S3H_OK;
+  s3h_crc_plan_destroy(H->p);
+  delete H;
+  return S3H_OK;
+}
+
+int s3h_crc64nvme_batch_device(int device, const void* d_base, const uint64_t* offsets,
+                               const uint64_t* lengths, uint64_t n, uint64_t* d_crcs, void* stream) {
+  if (int rc = check_batch_args(offsets, lengths, n)) return rc;
+  if (!d_base || !d_crcs) return fail(S3H_EINVAL, "crc64nvme batch: null argument");
+  s3h_crc_plan_s* P = nullptr;
+  if (int rc = crc_plan_build(device, kCrcIdCrc64Nvme, offsets, lengths, n, &P)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  int rc = crc_plan_launch(P, d_base, reinterpret_cast<uint32_t*>(d_crcs), s);
+  if (rc == S3H_OK) {
+    DeviceGuard g(device);
+    hipError_t e = hipStreamSynchronize(s);
+    if (e != hipSuccess) rc = fail(S3H_EHIP, "crc64nvme batch sync: %s", hipGetErrorString(e));
+  }
+  s3h_crc_plan_destroy(P);
+  return rc;
+}
+
+int s3h_crc64nvme_verify_batch_device(int device, const void* d_base, const uint64_t* offsets,
+                                      const uint64_t* lengths, uint64_t n, const uint64_t* d_expected,
+                                      uint8_t* d_mismatch, uint64_t* mismatches, void* stream) {
+  if (int rc = check_batch_args(offsets, lengths, n)) return rc;
+  if (!d_base || !d_expected || !d_mismatch || !mismatches)
+    return fail(S3H_EINVAL, "crc64nvme verify: null argument");
+  s3h_crc_plan_s* P = nullptr;
+  if (int rc = crc_plan_build(device, kCrcIdCrc64Nvme, offsets, lengths, n, &P)) return rc;
+  struct Cleanup {
+    s3h_crc_plan_s* P;
+    ~Cleanup() { s3h_crc_plan_destroy(P); }
+  } cleanup{P};
+  DeviceGuard g(device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  uint32_t* d_crcs = nullptr;
+  unsigned long long* d_count = nullptr;
+  HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&d_crcs), n * 8, s));
+  HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&d_count), 8, s));
+  HIP_TRY(hipMemsetAsync(d_count, 0, 8, s));
+  int rc = crc_plan_launch(P, d_base, d_crcs, s);
+  if (rc == S3H_OK) {
+    unsigned long long c = 0;
+    hipError_t e = launch_compare_digests(d_crcs, reinterpret_cast<const uint32_t*>(d_expected), n, 2,
+                                          d_mismatch, d_count, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(&c, d_count, 8, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) rc = fail(S3H_EHIP, "crc64nvme verify: %s", hipGetErrorString(e));
     *mismatches = c;
   }
   (void)hipFreeAsync(d_crcs, s);

@@ -8,14 +8,18 @@
 namespace s3h::host {
 
 // The host pipeline's algorithm ids: enum s3h_algo, and beside it (internal, never part of the
-// public enum) one id per enum s3h_crc.  A merged batch is keyed on the id array.
+// public enum) one id per enum s3h_crc and one for CRC-64/NVME (a CRC plan's id 2, internal.hpp
+// kCrcIdCrc64Nvme).  A merged batch is keyed on the id array.
 constexpr int kAlgoCrcBase = 0x100;
 constexpr int kAlgoCrc32c = kAlgoCrcBase + S3H_CRC32C, kAlgoCrc32 = kAlgoCrcBase + S3H_CRC32;
-inline bool is_crc(int algo) { return algo == kAlgoCrc32c || algo == kAlgoCrc32; }
-inline int crc_of(int algo) { return algo - kAlgoCrcBase; }  // the enum s3h_crc of a CRC id
+constexpr int kAlgoCrc64Nvme = kAlgoCrcBase + 2;
+inline bool is_crc(int algo) { return algo == kAlgoCrc32c || algo == kAlgoCrc32 || algo == kAlgoCrc64Nvme; }
+inline int crc_of(int algo) { return algo - kAlgoCrcBase; }  // the CRC plan's id of a CRC algorithm
 
-// digest words per part: SHA-256 8, MD5 4, a CRC 1
-inline uint32_t digest_words(int algo) { return algo == S3H_ALGO_MD5 ? 4u : is_crc(algo) ? 1u : 8u; }
+// digest words per part: SHA-256 8, MD5 4, a 32-bit CRC 1, CRC-64/NVME 2
+inline uint32_t digest_words(int algo) {
+  return algo == S3H_ALGO_MD5 ? 4u : algo == kAlgoCrc64Nvme ? 2u : is_crc(algo) ? 1u : 8u;
+}
 
 // algorithms one host-path call computes: SHA-256, MD5 or a CRC alone, or two of them
 constexpr int kHostMaxAlgo = 2;

@@ -9,7 +9,7 @@
 // sha256.cpp:84-144).  Many small parts go in groups of whole parts instead (run_host_groups).
 // An algorithm is SHA-256, MD5 or a CRC (host_limits.hpp is_crc): a CRC's "plan" is a CRC plan
 // and its resumable launch s3h_crc_plan_launch_range's, so SHA-256 and the x-amz-checksum-crc32c
-// / -crc32 value of a part come out of one pass over the host link.
+// / -crc32 / -crc64nvme value of a part come out of one pass over the host link.
 #include <fcntl.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -488,7 +488,7 @@ int run_host_groups(HostCtx& C, const HostShard& sh, const int* algos, int nalgo
       HIP_TRY(hipStreamWaitEvent(C.hash_s[a], C.copied[q], 0));
       if (is_crc(algos[a])) {  // whole parts: one ranged launch from byte 0 to the longest part's end
         s3h_crc_plan_s* R = C.gcrc[q][a];
-        if (int rc = crc_plan_launch_range(R, dgrp, C.d_dig[a] + j0, 0, std::max<uint64_t>(R->longest, 1), 0,
+        if (int rc = crc_plan_launch_range(R, dgrp, C.d_dig[a] + j0 * digest_words(algos[a]), 0, std::max<uint64_t>(R->longest, 1), 0,
                                            C.hash_s[a]))
           return rc;
       } else if (int rc = plan_launch(P, dgrp, C.d_dig[a] + j0 * digest_words(algos[a]), 0, P->max_blocks, 0,
@@ -614,7 +614,7 @@ int run_host_shard(HostCtx& C, const HostShard& sh, const int* algos, int nalgo,
       // the launch at byte 0), beside a digest over that digest's blocks
       HIP_TRY(C.ensure_crc_pin(n));
       if (int rc = C.ensure_crc(&C.crc[a], algos[a], n, crc_max_segments(lens.data(), n))) return rc;
-      HIP_TRY(C.ensure_digests(a, n * sizeof(uint32_t)));
+      HIP_TRY(C.ensure_digests(a, n * digest_words(algos[a]) * sizeof(uint32_t)));
       if (int rc = crc_plan_refill(C.crc[a], offs.data(), lens.data(), n, C.crc_parts(0, a),
                                    C.crc_offs(0, a), C.copy_s))
         return rc;
@@ -1011,6 +1011,34 @@ int s3h_sha256_crc_file_parts(int crc, const char* path, const uint64_t* offsets
   int algos[2] = {S3H_ALGO_SHA256, 0};
   if (int rc = crc_algo_id(crc, &algos[1])) return rc;
   uint32_t* const out[2] = {sha256_digests, crcs};
+  return file_parts(algos, 2, path, offsets, lengths, n, out, ndevices, slice_bytes);
+}
+
+// CRC-64/NVME: the same pipeline with two words per part (host_limits.hpp digest_words).
+int s3h_crc64nvme_batch_host(const uint8_t* const* parts, const uint64_t* lengths, uint64_t n,
+                             uint64_t* crcs, int ndevices, uint64_t slice_bytes) {
+  if (!parts || !lengths || !crcs || n == 0) return fail(S3H_EINVAL, "crc64nvme_batch_host: bad arguments");
+  return batch_host(kAlgoCrc64Nvme, parts, lengths, n, reinterpret_cast<uint32_t*>(crcs), ndevices,
+                    slice_bytes);
+}
+
+int s3h_sha256_crc64nvme_batch_host(const uint8_t* const* parts, const uint64_t* lengths, uint64_t n,
+                                    uint32_t* sha256_digests, uint64_t* crcs, int ndevices,
+                                    uint64_t slice_bytes) {
+  static const int algos[2] = {S3H_ALGO_SHA256, kAlgoCrc64Nvme};
+  if (!parts || !lengths || !sha256_digests || !crcs || n == 0)
+    return fail(S3H_EINVAL, "sha256_crc64nvme_batch_host: bad arguments");
+  uint32_t* const out[2] = {sha256_digests, reinterpret_cast<uint32_t*>(crcs)};
+  PartSource src;
+  src.parts = parts;
+  return batch_host(algos, 2, src, lengths, n, out, ndevices, slice_bytes);
+}
+
+int s3h_sha256_crc64nvme_file_parts(const char* path, const uint64_t* offsets, const uint64_t* lengths,
+                                    uint64_t n, uint32_t* sha256_digests, uint64_t* crcs, int ndevices,
+                                    uint64_t slice_bytes) {
+  static const int algos[2] = {S3H_ALGO_SHA256, kAlgoCrc64Nvme};
+  uint32_t* const out[2] = {sha256_digests, reinterpret_cast<uint32_t*>(crcs)};
   return file_parts(algos, 2, path, offsets, lengths, n, out, ndevices, slice_bytes);
 }
 

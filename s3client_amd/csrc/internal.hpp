@@ -8,7 +8,8 @@
 //   pinned.cpp    NUMA-placed pinned host memory, device placement, s3h_host_alloc / _numa
 //   host_path.cpp host-resident pipeline (slices, groups), per-device contexts, the merge queue
 //   stream.cpp    multi-object streams (s3h_stream_*)
-//   crc.cpp       CRC-32C / CRC-32 plans: whole-part and ranged launches (s3h_crc_*), the host path's plans
+//   crc.cpp       CRC-32C / CRC-32 / CRC-64/NVME plans: whole-part and ranged launches (s3h_crc_*,
+//                 s3h_crc64nvme_*), the host path's plans
 //   route.cpp     size-aware routing (model measurement, observed rates, routed entry points)
 //   HIP-free: status.cpp, topology.cpp, route_plan.cpp (+ copy_pool.hpp, host_queue.hpp)
 #pragma once
@@ -62,10 +63,15 @@ struct s3h_plan_s {
 
 // A CRC plan (crc.cpp).  Device arrays hold `cap` parts and `seg_cap` segment values and only
 // grow (the host path reuses its plans call after call, crc_plan_reserve / crc_plan_refill).
+// `crc` is an enum s3h_crc or kCrcIdCrc64Nvme; a 64-bit plan (words == 2) keeps its tables,
+// partials, running values and outputs as 64-bit words behind the same pointers.
+constexpr int kCrcIdCrc64Nvme = 2;  // internal id beside enum s3h_crc (never accepted by s3h_crc_*)
 struct s3h_crc_plan_s {
   int device = 0;
   int crc = S3H_CRC32C;
   uint32_t poly = 0;
+  uint64_t poly64 = 0;             // 64-bit plans
+  uint32_t words = 1;              // 32-bit words per value: 1, or 2 for CRC-64/NVME
   uint64_t n = 0;
   uint64_t nseg = 0;
   uint64_t cap = 0, seg_cap = 0;
@@ -82,6 +88,11 @@ struct s3h_crc_plan_s {
   uint32_t* d_partials = nullptr;
   uint32_t* d_state = nullptr;     // ranged launches: one running raw value per part
   uint64_t range_end = 0;          // byte_end of the last ranged launch (0: the next starts over)
+};
+// The public handle of a CRC-64/NVME plan: a type of its own, so a 64-bit plan cannot be handed
+// to the 32-bit launches by mistake.
+struct s3h_crc64nvme_plan_s {
+  s3h_crc_plan_s* p = nullptr;
 };
 
 namespace s3h::host {
@@ -159,13 +170,18 @@ hipError_t launch_crc(const s3h::CrcSegArgs& A, uint32_t seg_grid, const s3h::Cr
 // Both ranged stages on `s`; `piece_grid` workgroups of kCrcSegThreads for stage 1.
 hipError_t launch_crc_range(const s3h::CrcRangeArgs& A, uint32_t piece_grid, hipStream_t s);
 
+// The same for CRC-64/NVME (crc64_kernels.hip): A.segs set for the whole-part launch.
+hipError_t launch_crc64(const s3h::Crc64Args& A, uint32_t seg_grid, hipStream_t s);
+hipError_t launch_crc64_range(const s3h::Crc64Args& A, uint32_t piece_grid, hipStream_t s);
+
 // ------------------------------------------------------------------ CRC plans (crc.cpp)
 // The host path's use of a plan: created once per context with the tables uploaded
 // (crc_plan_alloc), grown to the call's parts and segment values (crc_plan_reserve, the only
 // step that allocates), its per-part records rewritten per call or group through pinned staging
 // on stream `s` (crc_plan_refill: h_parts / h_offs hold n entries each and stay untouched until
 // the copies have run), then ranged launches.  crc_max_segments bounds the segment values of
-// any segment size the plan may pick.
+// any segment size the plan may pick.  `crc` may be kCrcIdCrc64Nvme: d_crcs then receives
+// two words per part.
 int crc_plan_alloc(int device, int crc, s3h_crc_plan_s** out);
 uint64_t crc_max_segments(const uint64_t* lengths, uint64_t n);
 int crc_plan_reserve(s3h_crc_plan_s* P, uint64_t parts, uint64_t segments);

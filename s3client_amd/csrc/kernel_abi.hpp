@@ -147,6 +147,29 @@ struct CrcRangeArgs {
 constexpr int kCrcSegThreads = 512;   // 8 waves share one copy of the tables in LDS
 constexpr int kCrcPartThreads = 256;  // 4 parts per workgroup
 
+// ------------------------------------------------------------- CRC-64/NVME (crc64_kernels.hip)
+// The same two stages and the same per-segment / per-part records (CrcSeg, CrcPart) with 64-bit
+// values: tables (crc64_math.hpp build_device_tables), partials, running values and outputs are
+// 64-bit words.  One argument block serves the whole-part launch (segs set; begin, end, origin,
+// offs and state unused) and the ranged launch (segs null).
+struct Crc64Args {
+  const uint8_t* base;
+  const CrcSeg* segs;      // whole-part launch: one record per segment
+  const CrcPart* parts;
+  const uint64_t* offs;    // ranged launch: byte offset of each part relative to `base`
+  const uint64_t* tables;  // crc64_math.hpp kTableWords words, 16-B aligned
+  uint64_t* partials;      // one raw value per segment / piece
+  uint64_t* state;         // ranged launch: one running raw value per part
+  uint64_t* crcs;          // one finalised CRC per part, part order
+  uint64_t n, nseg;
+  uint64_t begin, end, origin;
+  uint64_t poly;
+  uint64_t x_segment;      // x^(8 * segment_bytes) mod P
+  uint32_t log2_segment;
+};
+constexpr int kCrc64SegThreads = 512;   // 8 waves share one copy of the tables (48.6 KiB of LDS)
+constexpr int kCrc64PartThreads = 256;  // 4 parts per workgroup
+
 // ------------------------------------------------------------- synthetic input generator
 // G(seed, p, L) of SURVEY.md 8(d): one record per part (byte offset, length, generator id).
 struct GenPart { uint64_t off, len, id; };

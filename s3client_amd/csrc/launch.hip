@@ -1,11 +1,12 @@
 // launch.hip -- the only translation unit with device code: the gfx950 kernels of
-// sha256_kernels.hip and crc32_kernels.hip and the launches that pick among them.  Everything around the launches --
+// sha256_kernels.hip, crc32_kernels.hip and crc64_kernels.hip and the launches that pick among them.  Everything around the launches --
 // plans, the host pipeline, streams, routing -- is host C++ in the other units (internal.hpp).
 #include <hip/hip_runtime.h>
 
 #include "internal.hpp"
 #include "sha256_kernels.hip"
 #include "crc32_kernels.hip"
+#include "crc64_kernels.hip"
 
 namespace s3h::host {
 
@@ -117,6 +118,23 @@ hipError_t launch_crc_range(const s3h::CrcRangeArgs& A, uint32_t piece_grid, hip
   constexpr uint64_t per_wg = s3h::kCrcPartThreads / 64;
   hipLaunchKernelGGL(s3h::crc_range_parts_kernel, dim3(uint32_t((A.n + per_wg - 1) / per_wg)),
                      dim3(s3h::kCrcPartThreads), 0, s, A);
+  return hipGetLastError();
+}
+
+hipError_t launch_crc64(const s3h::Crc64Args& A, uint32_t seg_grid, hipStream_t s) {
+  if (A.nseg != 0)  // (a batch of empty parts has no segments)
+    hipLaunchKernelGGL(s3h::crc64_segments_kernel, dim3(seg_grid), dim3(s3h::kCrc64SegThreads), 0, s, A);
+  constexpr uint64_t per_wg = s3h::kCrc64PartThreads / 64;
+  hipLaunchKernelGGL(s3h::crc64_parts_kernel, dim3(uint32_t((A.n + per_wg - 1) / per_wg)),
+                     dim3(s3h::kCrc64PartThreads), 0, s, A);
+  return hipGetLastError();
+}
+
+hipError_t launch_crc64_range(const s3h::Crc64Args& A, uint32_t piece_grid, hipStream_t s) {
+  hipLaunchKernelGGL(s3h::crc64_range_pieces_kernel, dim3(piece_grid), dim3(s3h::kCrc64SegThreads), 0, s, A);
+  constexpr uint64_t per_wg = s3h::kCrc64PartThreads / 64;
+  hipLaunchKernelGGL(s3h::crc64_range_parts_kernel, dim3(uint32_t((A.n + per_wg - 1) / per_wg)),
+                     dim3(s3h::kCrc64PartThreads), 0, s, A);
   return hipGetLastError();
 }
 

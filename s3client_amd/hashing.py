@@ -351,6 +351,13 @@ class CrcPlan:
     through a buffer the plan owns.  ``launch`` checksums whole parts; ``launch_range`` a byte
     range of every part, resumable (after a ``launch`` the next range must begin at 0)."""
 
+    _prefix = "s3h_crc_plan_"   # the C entry points of this plan type
+    _value_bytes = 4            # bytes per value in ``crcs``
+
+    def _create(self, h) -> int:
+        return lib().s3h_crc_plan_create(self.device, self.crc, _p64(self.offsets),
+                                         _p64(self.lengths), self.n, ctypes.byref(h))
+
     def __init__(self, offsets: Sequence[int], lengths: Sequence[int], device: int = 0,
                  algo: str | int = "crc32c"):
         self.crc = _crc_id(algo)
@@ -360,14 +367,13 @@ class CrcPlan:
         self.n = int(self.lengths.size)
         self.device = device
         h = ctypes.c_void_p()
-        check(lib().s3h_crc_plan_create(device, self.crc, _p64(self.offsets), _p64(self.lengths),
-                                        self.n, ctypes.byref(h)))
+        check(self._create(h))
         self._h = h
 
     def info(self) -> dict:
         n, segs, sb, g = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint32()
-        check(lib().s3h_crc_plan_info(self._h, ctypes.byref(n), ctypes.byref(segs),
-                                      ctypes.byref(sb), ctypes.byref(g)))
+        check(getattr(lib(), self._prefix + "info")(self._h, ctypes.byref(n), ctypes.byref(segs),
+                                                    ctypes.byref(sb), ctypes.byref(g)))
         return {"n": n.value, "segments": segs.value, "segment_bytes": sb.value, "grid": g.value}
 
     def launch(self, data, crcs, stream=None) -> None:
@@ -375,15 +381,15 @@ class CrcPlan:
         Asynchronous on ``stream``."""
         if not (data.is_cuda and crcs.is_cuda):
             raise ValueError("data and crcs must be device tensors")
-        if crcs.numel() * crcs.element_size() < 4 * self.n:
-            raise ValueError("crcs buffer too small (need n*4 bytes)")
+        if crcs.numel() * crcs.element_size() < self._value_bytes * self.n:
+            raise ValueError(f"crcs buffer too small (need n*{self._value_bytes} bytes)")
         end = int((self.offsets + self.lengths).max()) if self.n else 0
         if data.numel() * data.element_size() < end:
             raise ValueError(f"data buffer ({data.numel() * data.element_size()} B) smaller "
                              f"than the plan's extent ({end} B)")
-        check(lib().s3h_crc_plan_launch(self._h, ctypes.c_void_p(data.data_ptr()),
-                                        ctypes.c_void_p(crcs.data_ptr()),
-                                        ctypes.c_void_p(_stream_handle(stream))))
+        check(getattr(lib(), self._prefix + "launch")(self._h, ctypes.c_void_p(data.data_ptr()),
+                                                      ctypes.c_void_p(crcs.data_ptr()),
+                                                      ctypes.c_void_p(_stream_handle(stream))))
 
     def launch_range(self, data, crcs, byte_begin: int, byte_end: int, byte_origin: int = 0,
                      stream=None) -> None:
@@ -394,8 +400,8 @@ class CrcPlan:
         byte_begin is 0 (a new pass) or the previous ranged launch's byte_end."""
         if not (data.is_cuda and crcs.is_cuda):
             raise ValueError("data and crcs must be device tensors")
-        if crcs.numel() * crcs.element_size() < 4 * self.n:
-            raise ValueError("crcs buffer too small (need n*4 bytes)")
+        if crcs.numel() * crcs.element_size() < self._value_bytes * self.n:
+            raise ValueError(f"crcs buffer too small (need n*{self._value_bytes} bytes)")
         if byte_origin <= byte_begin < byte_end and self.n:  # (the library rejects the rest)
             top = np.minimum(self.lengths, np.uint64(byte_end))
             live = top > np.uint64(byte_begin)
@@ -403,14 +409,13 @@ class CrcPlan:
             if data.numel() * data.element_size() < end:
                 raise ValueError(f"data buffer ({data.numel() * data.element_size()} B) smaller "
                                  f"than the range's extent ({end} B)")
-        check(lib().s3h_crc_plan_launch_range(self._h, ctypes.c_void_p(data.data_ptr()),
-                                              ctypes.c_void_p(crcs.data_ptr()), byte_begin,
-                                              byte_end, byte_origin,
-                                              ctypes.c_void_p(_stream_handle(stream))))
+        check(getattr(lib(), self._prefix + "launch_range")(
+            self._h, ctypes.c_void_p(data.data_ptr()), ctypes.c_void_p(crcs.data_ptr()), byte_begin,
+            byte_end, byte_origin, ctypes.c_void_p(_stream_handle(stream))))
 
     def close(self) -> None:
         if getattr(self, "_h", None):
-            lib().s3h_crc_plan_destroy(self._h)
+            getattr(lib(), self._prefix + "destroy")(self._h)
             self._h = None
 
     def __del__(self):
@@ -535,6 +540,143 @@ def checksum_text(part_crcs, algo: str | int = "crc32c", composite: bool = False
     out = ctypes.create_string_buffer(_native.CHECKSUM_MAX)
     check(lib().s3h_checksum_text(_crc_id(algo), ctypes.c_void_p(w.ctypes.data), w.size,
                                   int(bool(composite)), out, len(out)))
+    return out.value.decode()
+
+
+# ------------------------------------------------------------------ CRC-64/NVME checksum
+class Crc64Plan(CrcPlan):
+    """CrcPlan for CRC-64/NVME (x-amz-checksum-crc64nvme; s3h_crc64nvme_plan_create): the same
+    ``launch`` / ``launch_range`` / ``info``, with ``crcs`` holding n 64-bit words."""
+
+    _prefix = "s3h_crc64nvme_plan_"
+    _value_bytes = 8
+
+    def _create(self, h) -> int:
+        return lib().s3h_crc64nvme_plan_create(self.device, _p64(self.offsets), _p64(self.lengths),
+                                               self.n, ctypes.byref(h))
+
+    def __init__(self, offsets: Sequence[int], lengths: Sequence[int], device: int = 0):
+        self.crc = _native.CRC64NVME
+        self.offsets, self.lengths = _u64(offsets), _u64(lengths)
+        if self.offsets.shape != self.lengths.shape or self.offsets.ndim != 1:
+            raise ValueError("offsets and lengths must be 1-D and of equal length")
+        self.n = int(self.lengths.size)
+        self.device = device
+        h = ctypes.c_void_p()
+        check(self._create(h))
+        self._h = h
+
+
+def crc64_batch_device(data, offsets, lengths, stream=None):
+    """CRC-64/NVME of every part [offsets[i], offsets[i]+lengths[i]) of the device tensor
+    ``data`` (any byte alignment): an (n,) int64 device tensor holding the uint64 values
+    (``.cpu().numpy().view(np.uint64)``).  Blocking."""
+    import torch
+    offs, lens = _u64(offsets), _u64(lengths)
+    end = int((offs + lens).max()) if offs.size else 0
+    if not data.is_cuda or data.numel() * data.element_size() < end:
+        raise ValueError("data must be a device tensor that covers every part")
+    out = torch.empty(offs.size, dtype=torch.int64, device=data.device)
+    check(lib().s3h_crc64nvme_batch_device(data.device.index, ctypes.c_void_p(data.data_ptr()),
+                                           _p64(offs), _p64(lens), offs.size,
+                                           ctypes.c_void_p(out.data_ptr()),
+                                           ctypes.c_void_p(_stream_handle(stream))))
+    return out
+
+
+def crc64_verify_batch_device(data, offsets, lengths, expected, stream=None):
+    """Device-resident verification against ``expected`` (n 64-bit words, device): returns
+    (mismatch count, bool mask on the device)."""
+    import torch
+    offs, lens = _u64(offsets), _u64(lengths)
+    if expected.numel() * expected.element_size() < 8 * offs.size:
+        raise ValueError("expected buffer too small (need n*8 bytes)")
+    mism = torch.zeros(offs.size, dtype=torch.uint8, device=data.device)
+    cnt = ctypes.c_uint64(0)
+    check(lib().s3h_crc64nvme_verify_batch_device(data.device.index,
+                                                  ctypes.c_void_p(data.data_ptr()), _p64(offs),
+                                                  _p64(lens), offs.size,
+                                                  ctypes.c_void_p(expected.data_ptr()),
+                                                  ctypes.c_void_p(mism.data_ptr()),
+                                                  ctypes.byref(cnt),
+                                                  ctypes.c_void_p(_stream_handle(stream))))
+    return cnt.value, mism.bool()
+
+
+def crc64_batch_host(parts: Sequence, ndevices: int = 0, slice_bytes: int = 0) -> np.ndarray:
+    """CRC-64/NVME of host-resident parts on the GPUs (s3h_crc64nvme_batch_host): (n,) uint64."""
+    arrs, ptrs, lens = _host_parts(parts)
+    n = len(arrs)
+    out = np.zeros(n, dtype=np.uint64)
+    check(lib().s3h_crc64nvme_batch_host(ptrs, _p64(lens), n, out.ctypes.data, ndevices, slice_bytes))
+    return out
+
+
+def sha256_crc64_batch_host(parts: Sequence, ndevices: int = 0,
+                            slice_bytes: int = 0) -> tuple[np.ndarray, np.ndarray]:
+    """SHA-256 (n, 8) digests and CRC-64/NVME values (n,) uint64 of host-resident parts, each
+    part crossing PCIe once (s3h_sha256_crc64nvme_batch_host)."""
+    arrs, ptrs, lens = _host_parts(parts)
+    n = len(arrs)
+    sha = np.zeros((n, DIGEST_WORDS), dtype=np.uint32)
+    out = np.zeros(n, dtype=np.uint64)
+    check(lib().s3h_sha256_crc64nvme_batch_host(ptrs, _p64(lens), n, sha.ctypes.data,
+                                                out.ctypes.data, ndevices, slice_bytes))
+    return sha, out
+
+
+def sha256_crc64_file_parts(path: str, offsets, lengths, ndevices: int = 0,
+                            slice_bytes: int = 0) -> tuple[np.ndarray, np.ndarray]:
+    """SHA-256 (n, 8) digests and CRC-64/NVME values (n,) of file ranges, each slice read once
+    (s3h_sha256_crc64nvme_file_parts)."""
+    offs, lens = _u64(offsets), _u64(lengths)
+    if offs.shape != lens.shape or offs.ndim != 1 or offs.size == 0:
+        raise ValueError("offsets and lengths must be 1-D, equal length and non-empty")
+    sha = np.zeros((offs.size, DIGEST_WORDS), dtype=np.uint32)
+    out = np.zeros(offs.size, dtype=np.uint64)
+    check(lib().s3h_sha256_crc64nvme_file_parts(os.fsencode(path), _p64(offs), _p64(lens), offs.size,
+                                                sha.ctypes.data, out.ctypes.data, ndevices,
+                                                slice_bytes))
+    return sha, out
+
+
+_M64 = 0xFFFFFFFFFFFFFFFF
+
+
+def crc64(data, seed: int = 0) -> int:
+    """CPU CRC-64/NVME of one message (s3h_cpu_crc64nvme); ``seed`` = a previous call's result,
+    so chunks chain."""
+    a = _as_bytes(data) if isinstance(data, np.ndarray) else np.frombuffer(bytes(data), dtype=np.uint8)
+    return int(lib().s3h_cpu_crc64nvme(ctypes.c_void_p(a.ctypes.data if a.size else None), a.size,
+                                       seed & _M64))
+
+
+def crc64_combine(crc_a: int, crc_b: int, len_b: int) -> int:
+    """crc(A || B) from crc(A), crc(B) and len(B) (s3h_crc64nvme_combine)."""
+    out = ctypes.c_uint64()
+    check(lib().s3h_crc64nvme_combine(crc_a & _M64, crc_b & _M64, int(len_b), ctypes.byref(out)))
+    return out.value
+
+
+def crc64_object(part_crcs, lengths) -> int:
+    """FULL_OBJECT x-amz-checksum-crc64nvme value of the parts' concatenation from their CRCs
+    and lengths (s3h_crc64nvme_object)."""
+    if isinstance(part_crcs, np.ndarray) and part_crcs.dtype == np.int64:
+        part_crcs = part_crcs.view(np.uint64)  # (the int64 view of a device tensor's values)
+    w = np.ascontiguousarray(np.asarray(part_crcs, dtype=np.uint64)).reshape(-1)
+    lens = _u64(lengths)
+    if lens.shape != w.shape:
+        raise ValueError("one length per part checksum")
+    out = ctypes.c_uint64()
+    check(lib().s3h_crc64nvme_object(ctypes.c_void_p(w.ctypes.data), _p64(lens), w.size,
+                                     ctypes.byref(out)))
+    return out.value
+
+
+def checksum64_text(crc: int) -> str:
+    """Header text of a 64-bit checksum (s3h_checksum64_text): base64 of its 8 big-endian bytes."""
+    out = ctypes.create_string_buffer(_native.CHECKSUM_MAX)
+    check(lib().s3h_checksum64_text(int(crc) & _M64, out, len(out)))
     return out.value.decode()
 
 

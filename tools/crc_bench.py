@@ -7,11 +7,16 @@ product benchmark: bench.py is untouched).  One process, profiler off, device-re
   * a read-roof kernel (tools/crc_roof.hip, this tool's own): the CRC segment kernel's grid,
     segment table and dwordx4 loads, XOR-reduced.
 
+With --crc64 the same run also times CRC-64/NVME (crc64_kernels.hip) on both shapes and, beside
+CRC-32C, on a ragged batch (one 64 MiB part plus 4,096 parts of U[1, 128] KiB), and writes
+profiles/crc64_c2.json instead: its rate, its ratio to the read roof and to CRC-32C of the run.
+
 Every item is warmed up, then timed with HIP events in rounds that alternate between the items
 until each has at least --seconds of GPU time.  Every digest timed is checked against the CPU
 value before its rate is recorded.  Writes one JSON document (default profiles/crc_c2.json).
 
     make crcbench && python tools/crc_bench.py [--out profiles/crc_c2.json] [--git-head SHA]
+    make crcbench && python tools/crc_bench.py --crc64 [--out profiles/crc64_c2.json]
 """
 import argparse
 import ctypes
@@ -41,13 +46,17 @@ def segment_table(offs, lens, S):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "crc_c2.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--crc64", action="store_true",
+                    help="also time CRC-64/NVME and the ragged batch; default output profiles/crc64_c2.json")
     ap.add_argument("--seconds", type=float, default=2.0)
     ap.add_argument("--parts", type=int, default=1024)
     ap.add_argument("--part-mib", type=int, default=8)
     ap.add_argument("--big-mib", type=int, default=1024)
     ap.add_argument("--git-head", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "crc64_c2.json" if args.crc64 else "crc_c2.json")
     import torch
 
     import s3client_amd as s3
@@ -89,6 +98,16 @@ def main():
                 "check": (lambda out=out, want=want: np.array_equal(out.cpu().numpy().view(np.uint32), want)),
                 "info": info}
             keep.append(plan)
+        if args.crc64:
+            plan = s3.Crc64Plan(o, l)
+            out = torch.empty(len(l), dtype=torch.int64, device="cuda")
+            want = np.array(cpu(s3.crc64, o, l), dtype=np.uint64)
+            items[f"crc64nvme_{shape}"] = {
+                "launch": (lambda p=plan, out=out: p.launch(data, out)), "bytes": int(l.sum()),
+                "check": (lambda out=out, want=want: np.array_equal(out.cpu().numpy().view(np.uint64), want)),
+                "info": plan.info()}
+            assert plan.info()["segment_bytes"] == info["segment_bytes"]
+            keep.append(plan)
         segs = segment_table(o, l, info["segment_bytes"])
         assert len(segs) == info["segments"]
         d_segs = torch.from_numpy(segs.view(np.uint8)).cuda()
@@ -99,6 +118,22 @@ def main():
                        roof.crc_roof_launch(data.data_ptr(), d_segs.data_ptr(), k, g, d_out.data_ptr(), stream)),
             "bytes": int(l.sum()), "info": {"grid": info["grid"], "segments": len(segs)},
             "check": (lambda d_out=d_out, want=want: np.array_equal(d_out.cpu().numpy().view(np.uint32), want))}
+    if args.crc64:  # ragged: one 64 MiB part, then 4,096 parts of U[1, 128] KiB, back to back
+        rl = np.concatenate([[64 << 20], np.random.default_rng(SEED).integers(1, (128 << 10) + 1, 4096)]).astype(np.uint64)
+        ro = np.concatenate([[0], np.cumsum(rl)[:-1]]).astype(np.uint64)
+        assert int(rl.sum()) <= n * L
+        shapes["ragged"] = (ro, rl)
+        for name, mk, dt, fn in (("crc32c", lambda: s3.CrcPlan(ro, rl, algo="crc32c"), np.uint32,
+                                  lambda b: s3.crc(b, "crc32c")),
+                                 ("crc64nvme", lambda: s3.Crc64Plan(ro, rl), np.uint64, s3.crc64)):
+            plan = mk()
+            out = torch.empty(len(rl), dtype=torch.int32 if dt is np.uint32 else torch.int64, device="cuda")
+            want = np.array(cpu(fn, ro, rl), dtype=dt)
+            items[f"{name}_ragged"] = {
+                "launch": (lambda p=plan, out=out: p.launch(data, out)), "bytes": int(rl.sum()),
+                "check": (lambda out=out, want=want, dt=dt: np.array_equal(out.cpu().numpy().view(dt), want)),
+                "info": plan.info()}
+            keep.append(plan)
     for algo, words, fn in (("md5", 4, s3.md5), ("sha256", 8, s3.sha256)):
         plan = s3.Plan(offs, lens, algo=algo)
         out = torch.empty((n, words), dtype=torch.int32, device="cuda")
@@ -151,6 +186,7 @@ def main():
     doc = {
         "tool": "tools/crc_bench.py", "device": torch.cuda.get_device_name(0),
         "config": {"c2": f"{n} x {args.part_mib} MiB", "one_part": f"1 x {args.big_mib} MiB",
+                   **({"ragged": "1 x 64 MiB + 4096 x U[1, 128] KiB"} if args.crc64 else {}),
                    "seconds_per_item": args.seconds, "timing": "HIP events, items alternated per round"},
         "GiB_per_s": {k: round(v, 1) for k, v in rates.items()},
         "launches": {k: it["launches"] for k, it in items.items()},
@@ -158,12 +194,17 @@ def main():
         "plans": {k: it["info"] for k, it in items.items()},
         "segment_bytes": {s: items[f"crc32c_{s}"]["info"]["segment_bytes"] for s in shapes},
         "crc_over_read_roof": {f"{a}_{s}": round(rates[f"{a}_{s}"] / rates[f"roof_{s}"], 3)
-                               for a in ("crc32c", "crc32") for s in shapes},
-        "crc32c_over_md5_c2": {s: round(rates[f"crc32c_{s}"] / md5, 2) for s in shapes},
-        "bar": BAR, "bar_met": all(rates[f"crc32c_{s}"] >= BAR * md5 for s in shapes),
+                               for a in ("crc32c", "crc32") + (("crc64nvme",) if args.crc64 else ())
+                               for s in ("c2", "one_part")},
+        "crc32c_over_md5_c2": {s: round(rates[f"crc32c_{s}"] / md5, 2) for s in ("c2", "one_part")},
+        "bar": BAR, "bar_met": all(rates[f"crc32c_{s}"] >= BAR * md5 for s in ("c2", "one_part")),
+        **({"crc64nvme_over_crc32c": {s: round(rates[f"crc64nvme_{s}"] / rates[f"crc32c_{s}"], 3) for s in shapes},
+            "ragged_ms_per_launch": {a: round(items[f"{a}_ragged"]["ms"] / items[f"{a}_ragged"]["launches"], 4)
+                                     for a in ("crc32c", "crc64nvme")}} if args.crc64 else {}),
         "checked_against_cpu": sorted(items),
         "kernel_code_hash": {k: hashes.get(k) for k in ("crc_segments", "crc_parts", "md5-pc", "md5-pc1",
-                                                         "skew", "skew_nc2", "skewp", "skews")},
+                                                         "skew", "skew_nc2", "skewp", "skews") +
+                             (("crc64_segments", "crc64_parts") if args.crc64 else ())},
         "library_sha256": file_sha256(_native.LIB_PATH), "git_head": head,
     }
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

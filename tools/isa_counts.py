@@ -54,6 +54,11 @@ ALL_KERNELS = {
     "crc_parts": "_ZN3s3h16crc_parts_kernelENS_11CrcPartArgsE",
     "crc_range_pieces": "_ZN3s3h23crc_range_pieces_kernelENS_12CrcRangeArgsE",
     "crc_range_parts": "_ZN3s3h22crc_range_parts_kernelENS_12CrcRangeArgsE",
+    # CRC-64/NVME (crc64_kernels.hip): code hashes only
+    "crc64_segments": "_ZN3s3h21crc64_segments_kernelENS_9Crc64ArgsE",
+    "crc64_parts": "_ZN3s3h18crc64_parts_kernelENS_9Crc64ArgsE",
+    "crc64_range_pieces": "_ZN3s3h25crc64_range_pieces_kernelENS_9Crc64ArgsE",
+    "crc64_range_parts": "_ZN3s3h24crc64_range_parts_kernelENS_9Crc64ArgsE",
 }
 FLAG_KERNELS = ("skew_nc2", "skews", "dual_group", "dual_group_skew", "dual_group_mixed")
 ERR_STORE = re.compile(r"^\t(global|flat|buffer)_atomic_or\b")
