@@ -25,11 +25,14 @@ hipError_t launch_plan_kernel(const s3h_plan_s* P, int cus, uint64_t range, cons
   else if (P->algo == S3H_ALGO_MD5)  // more workgroups than CUs: the 32 KiB form, several per CU
     hipLaunchKernelGGL(s3h::md5_pc_kernel<1>, dim3(P->grid), dim3(s3h::kPcThreads), 0, stream, A);
   // The skew kernel counts a launch's blocks in 32 bits: a range of 2^31 blocks (128 GiB of
-  // one part) or more runs on the quad kernel (same plan geometry, 64-bit counters).
+  // one part) or more runs on the quad kernel (same slots and state, 64-bit counters).  The
+  // quad kernel reads its workgroup's first slot before any bounds check, so its grid is the
+  // one its own slot mapping needs (16 slots per workgroup at two waves), never the plan's: a
+  // two-group skew plan with solo workgroups has more workgroups than ceil(n / 16).
   else if (P->kernel == S3H_KERNEL_SKEW && range >= (1ull << 31) && P->quad_waves == 1)
-    hipLaunchKernelGGL(s3h::sha256_quad_kernel<1>, dim3(P->grid), dim3(128), 0, stream, A);
+    hipLaunchKernelGGL(s3h::sha256_quad_kernel<1>, dim3(uint32_t((P->n + 7) / 8)), dim3(128), 0, stream, A);
   else if (P->kernel == S3H_KERNEL_SKEW && range >= (1ull << 31))
-    hipLaunchKernelGGL(s3h::sha256_quad_kernel<2>, dim3(P->grid), dim3(192), 0, stream, A);
+    hipLaunchKernelGGL(s3h::sha256_quad_kernel<2>, dim3(uint32_t((P->n + 15) / 16)), dim3(192), 0, stream, A);
   else if (P->kernel == S3H_KERNEL_SKEWS && range >= (1ull << 31))
     hipLaunchKernelGGL(s3h::sha256_quad_kernel<1>, dim3(uint32_t((P->n + 7) / 8)), dim3(128), 0, stream, A);
   else if (P->kernel == S3H_KERNEL_SKEWS)
