@@ -21,11 +21,11 @@ LIB := $(LIBDIR)/libs3hash.so
 
 all: $(LIB) oracle cpptests
 
-# libs3hash.so = one device unit (launch.hip: the kernels of sha256_kernels.hip and
+# libs3hash.so = one device unit (launch.hip: the kernels of sha256_kernels.hip, sha1_kernels.hip and
 # crc32_kernels.hip / crc64_kernels.hip and their launches) + host units by concern (internal.hpp lists them) + the CPU drop-in.
 HOST_UNITS := status topology plan pinned host_path stream route_plan route crc
 HOST_OBJS := $(HOST_UNITS:%=$(OBJDIR)/%.o)
-CPU_OBJS := $(OBJDIR)/lib_hash.o $(OBJDIR)/lib_md5.o $(OBJDIR)/lib_crc.o $(OBJDIR)/lib_crc64.o
+CPU_OBJS := $(OBJDIR)/lib_hash.o $(OBJDIR)/lib_md5.o $(OBJDIR)/lib_crc.o $(OBJDIR)/lib_crc64.o $(OBJDIR)/lib_sha1.o
 KERNEL_OBJ := $(OBJDIR)/launch.o
 
 # The chain-loop instruction counts bench.py reports, the kernels' code hashes and the
@@ -34,7 +34,7 @@ KERNEL_OBJ := $(OBJDIR)/launch.o
 ISA_DIS := build/isa/libs3hash_gfx950.dis
 # (explicit prerequisites: the -MMD file is written from build/isa, so its relative paths do not
 # resolve from the repo root)
-KERNEL_SRCS := $(CSRC)/launch.hip $(CSRC)/sha256_kernels.hip $(CSRC)/crc32_kernels.hip $(CSRC)/crc64_kernels.hip $(wildcard $(CSRC)/*.inc) \
+KERNEL_SRCS := $(CSRC)/launch.hip $(CSRC)/sha256_kernels.hip $(CSRC)/sha1_kernels.hip $(CSRC)/crc32_kernels.hip $(CSRC)/crc64_kernels.hip $(wildcard $(CSRC)/*.inc) \
                $(CSRC)/crc_math.hpp $(CSRC)/crc64_math.hpp $(CSRC)/sha256_device.hpp $(CSRC)/kernel_abi.hpp $(CSRC)/exp_config.hpp $(CSRC)/internal.hpp
 $(KERNEL_OBJ): $(KERNEL_SRCS)
 	@mkdir -p $(OBJDIR) build/isa
@@ -102,6 +102,7 @@ exp:
 	$(CXX) $(CXXFLAGS) -c -o $(EXPDIR)/lib_md5.o $(CSRC)/cpu/lib_md5.cpp
 	$(CXX) $(CXXFLAGS) -c -o $(EXPDIR)/lib_crc.o $(CSRC)/cpu/lib_crc.cpp
 	$(CXX) $(CXXFLAGS) -c -o $(EXPDIR)/lib_crc64.o $(CSRC)/cpu/lib_crc64.cpp
+	$(CXX) $(CXXFLAGS) -c -o $(EXPDIR)/lib_sha1.o $(CSRC)/cpu/lib_sha1.cpp
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o tools/exp/libs3hash_$(TAG).so $(EXPDIR)/*.o -lpthread
 
 # Read-roof kernel of tools/crc_bench.py: the tool's own small library, never the product.

@@ -15,6 +15,10 @@
  *       lib/src/aws_sign.cpp:236-237 x-amz-content-sha256).
  *   s3h_plan_launch_range  -- resumable chaining state: sha256::sha256_stream semantics
  *       (lib/hash/sha256.h:97, sha256.cpp:84-144) for many parts at once.
+ *   s3h_sha1_batch_device / _batch_host / _file_parts, s3h_sha256_sha1_batch_host /
+ *       _file_parts, S3H_ALGO_SHA1 in s3h_plan_create_ex / s3h_stream_create / s3h_verify_*,
+ *       s3h_cpu_sha1, s3h_digest_checksum_text  -- x-amz-checksum-sha1 (lib/hash has no SHA-1;
+ *       FIPS 180-4): 5 words per part in the same word convention.
  *
  * Digest layout (every entry point): 8 uint32 words per part with word i = bswap32(H_i),
  * exactly lib/hash's `to_little` output (sha256.h:103-106); on little-endian hosts the 32
@@ -36,7 +40,9 @@ extern "C" {
  * points (s3h_crc_*, s3h_cpu_crc, s3h_checksum_text), then s3h_crc_plan_launch_range and the
  * host-resident forms s3h_crc_batch_host, s3h_sha256_crc_batch_host, s3h_sha256_crc_file_parts,
  * then CRC-64/NVME (s3h_crc64nvme_*, s3h_cpu_crc64nvme, s3h_checksum64_text,
- * s3h_sha256_crc64nvme_*). */
+ * s3h_sha256_crc64nvme_*), then SHA-1 (S3H_ALGO_SHA1 for plans, streams and verification,
+ * s3h_sha1_batch_device, s3h_sha1_batch_host, s3h_sha1_file_parts, s3h_sha256_sha1_batch_host,
+ * s3h_sha256_sha1_file_parts, s3h_cpu_sha1, s3h_digest_checksum_text). */
 #define S3H_API_VERSION 2
 
 enum s3h_status {
@@ -60,7 +66,8 @@ enum s3h_kernel {
 
 enum s3h_algo {
   S3H_ALGO_SHA256 = 0, /* payload SHA-256 (x-amz-content-sha256), digests n x 8 words */
-  S3H_ALGO_MD5 = 1     /* MD5 (Content-MD5, multipart ETags), digests n x 4 words */
+  S3H_ALGO_MD5 = 1,    /* MD5 (Content-MD5, multipart ETags), digests n x 4 words */
+  S3H_ALGO_SHA1 = 2    /* SHA-1 (x-amz-checksum-sha1), digests n x 5 words, word i = bswap32(H_i) */
 };
 
 /* What AUTO optimises when several kernels fit a batch (s3h_kernel_policy).  They differ only
@@ -200,7 +207,9 @@ typedef struct s3h_plan_s *s3h_plan_t;
 
 int s3h_plan_create(int device, const uint64_t *offsets, const uint64_t *lengths, uint64_t n,
                     int kernel, s3h_plan_t *plan);
-/* Same for any algorithm (s3h_algo); digests are 8 (SHA-256) or 4 (MD5) words per part. */
+/* Same for any algorithm (s3h_algo); digests are 8 (SHA-256), 4 (MD5) or 5 (SHA-1) words per
+ * part.  MD5 and SHA-1 have one kernel each: S3H_KERNEL_AUTO or S3H_KERNEL_PC, any other is
+ * S3H_EINVAL. */
 int s3h_plan_create_ex(int device, int algo, const uint64_t *offsets, const uint64_t *lengths,
                        uint64_t n, int kernel, s3h_plan_t *plan);
 int s3h_plan_algo(s3h_plan_t plan);
@@ -657,6 +666,43 @@ int s3h_crc64nvme_object(const uint64_t *part_crcs, const uint64_t *lengths, uin
  * x-amz-checksum-crc64nvme, base64 of the CRC's 8 bytes, big-endian (12 characters) -- of a
  * part, or of s3h_crc64nvme_object's result. */
 int s3h_checksum64_text(uint64_t crc, char *out, uint64_t out_len);
+
+/* ---------------------------------------------------------------- SHA-1 checksum
+ * x-amz-checksum-sha1 (objects stored with ChecksumAlgorithm=SHA1).  Digests are 5 uint32 words
+ * per part with word i = bswap32(H_i): the 20 bytes in memory are the canonical digest, the
+ * convention of SHA-256.  Plans (s3h_plan_create_ex with S3H_ALGO_SHA1: whole and ranged
+ * launches, status, info), streams (s3h_stream_create) and s3h_verify_batch_device /
+ * s3h_verify_batch_host take the algorithm id; the entry points below have the arguments and
+ * errors of their MD5 namesakes.  The routed calls (AUTO / CPU / SPLIT) do not take SHA-1:
+ * S3H_EINVAL.  Added within API version 2. */
+/* One-shot, blocking: plan + launch + sync.  d_digests: n x 5 words (4-byte aligned). */
+int s3h_sha1_batch_device(int device, const void *d_base, const uint64_t *offsets,
+                          const uint64_t *lengths, uint64_t n, uint32_t *d_digests, void *stream);
+int s3h_sha1_batch_host(const uint8_t *const *parts, const uint64_t *lengths, uint64_t n,
+                        uint32_t *digests, int ndevices, uint64_t slice_bytes);
+int s3h_sha1_file_parts(const char *path, const uint64_t *offsets, const uint64_t *lengths,
+                        uint64_t n, uint32_t *digests, int ndevices, uint64_t slice_bytes);
+/* x-amz-content-sha256 AND x-amz-checksum-sha1 of every part from one pass over the host link
+ * (two kernels on two hash streams per slice or group).  sha256_digests: n x 8 words;
+ * sha1_digests: n x 5 words. */
+int s3h_sha256_sha1_batch_host(const uint8_t *const *parts, const uint64_t *lengths, uint64_t n,
+                               uint32_t *sha256_digests, uint32_t *sha1_digests, int ndevices,
+                               uint64_t slice_bytes);
+int s3h_sha256_sha1_file_parts(const char *path, const uint64_t *offsets, const uint64_t *lengths,
+                               uint64_t n, uint32_t *sha256_digests, uint32_t *sha1_digests,
+                               int ndevices, uint64_t slice_bytes);
+/* CPU, one message: SHA-NI when the CPU has it, else portable scalar code (S3H_CPU_SCALAR=1
+ * forces the scalar path; s3h_cpu_backend names the choice).  Same word convention. */
+void s3h_cpu_sha1(const uint8_t *data, uint64_t length, uint32_t hash[5]);
+/* Header text of a digest checksum, NUL-terminated, out_len >= S3H_DIGEST_CHECKSUM_MAX.
+ * algo: S3H_ALGO_SHA1 or S3H_ALGO_SHA256 (MD5: S3H_EINVAL, see s3h_multipart_etag); digests:
+ * n x 5 or n x 8 words as the batch entry points return them.  composite = 0: n must be 1, the
+ * value of x-amz-checksum-sha1 / -sha256 of a part or a single-PUT object (base64 of the 20 or
+ * 32 digest bytes).  composite = 1: the COMPOSITE checksum of a multipart object, base64 of
+ * the same hash over the n raw digests concatenated, then "-n".  CPU only. */
+#define S3H_DIGEST_CHECKSUM_MAX 64
+int s3h_digest_checksum_text(int algo, const uint32_t *digests, uint64_t n, int composite,
+                             char *out, uint64_t out_len);
 
 /* ---------------------------------------------------------------- synthetic inputs
  * Fill part i (at d_base + offsets[i], 8-B aligned, lengths[i] bytes) with generator

@@ -449,3 +449,100 @@ inline std::string checksum_text(uint64_t value) {
 }
 
 }  // namespace crc64
+
+// x-amz-checksum-sha1 (SHA-1): 5 words per part with word i = bswap32(H_i), so the 20 bytes in
+// memory are the canonical digest (the convention of the SHA-256 digests).
+namespace sha1 {
+
+// Parts already in device memory at d_base + offsets[i] (any alignment); n x 5 words to d_digests.
+inline void sha1_batch_device(int device, const void* d_base, const std::vector<uint64_t>& offsets,
+                              const std::vector<uint64_t>& lengths, uint32_t* d_digests,
+                              void* stream = nullptr) {
+  if (offsets.size() != lengths.size()) throw std::invalid_argument("offsets/lengths size mismatch");
+  sha256::batch_check(s3h_sha1_batch_device(device, d_base, offsets.data(), lengths.data(),
+                                            offsets.size(), d_digests, stream));
+}
+
+// Host-resident parts on the GPUs (s3h_sha1_batch_host): 5 words per part.
+inline std::vector<uint32_t> sha1_batch(const std::vector<const uint8_t*>& parts,
+                                        const std::vector<uint64_t>& lengths, int ndevices = 0,
+                                        uint64_t slice_bytes = 0) {
+  if (parts.size() != lengths.size()) throw std::invalid_argument("parts/lengths size mismatch");
+  std::vector<uint32_t> d(5 * parts.size());
+  if (!parts.empty())
+    sha256::batch_check(s3h_sha1_batch_host(parts.data(), lengths.data(), parts.size(), d.data(),
+                                            ndevices, slice_bytes));
+  return d;
+}
+
+// (file, offset, size) parts (s3h_sha1_file_parts).
+inline std::vector<uint32_t> file_part_sha1(const std::string& path, const std::vector<uint64_t>& offsets,
+                                            const std::vector<uint64_t>& lengths, int ndevices = 0) {
+  if (offsets.size() != lengths.size()) throw std::invalid_argument("offsets/lengths size mismatch");
+  std::vector<uint32_t> d(5 * offsets.size());
+  if (!offsets.empty())
+    sha256::batch_check(s3h_sha1_file_parts(path.c_str(), offsets.data(), lengths.data(),
+                                            offsets.size(), d.data(), ndevices, 0));
+  return d;
+}
+
+// x-amz-content-sha256 and x-amz-checksum-sha1 per part from one pass over the host link.
+struct Sha256Sha1 {
+  std::vector<uint32_t> sha256;  // 8 words per part, lib/hash layout
+  std::vector<uint32_t> sha1;    // 5 words per part
+};
+inline Sha256Sha1 sha256_sha1_batch(const std::vector<const uint8_t*>& parts,
+                                    const std::vector<uint64_t>& lengths, int ndevices = 0,
+                                    uint64_t slice_bytes = 0) {
+  if (parts.size() != lengths.size()) throw std::invalid_argument("parts/lengths size mismatch");
+  Sha256Sha1 d{std::vector<uint32_t>(8 * parts.size()), std::vector<uint32_t>(5 * parts.size())};
+  if (!parts.empty())
+    sha256::batch_check(s3h_sha256_sha1_batch_host(parts.data(), lengths.data(), parts.size(),
+                                                   d.sha256.data(), d.sha1.data(), ndevices,
+                                                   slice_bytes));
+  return d;
+}
+
+inline Sha256Sha1 file_part_sha256_sha1(const std::string& path, const std::vector<uint64_t>& offsets,
+                                        const std::vector<uint64_t>& lengths, int ndevices = 0) {
+  if (offsets.size() != lengths.size()) throw std::invalid_argument("offsets/lengths size mismatch");
+  Sha256Sha1 d{std::vector<uint32_t>(8 * offsets.size()), std::vector<uint32_t>(5 * offsets.size())};
+  if (!offsets.empty())
+    sha256::batch_check(s3h_sha256_sha1_file_parts(path.c_str(), offsets.data(), lengths.data(),
+                                                   offsets.size(), d.sha256.data(), d.sha1.data(),
+                                                   ndevices, 0));
+  return d;
+}
+
+// One message on the CPU: 5 words.
+inline std::vector<uint32_t> sha1(const uint8_t* data, uint64_t length) {
+  if (!data && length) throw std::invalid_argument("sha1: null data");
+  std::vector<uint32_t> h(5);
+  s3h_cpu_sha1(data, length, h.data());
+  return h;
+}
+
+// Header value of one digest (`algo`: S3H_ALGO_SHA1, 5 words, or S3H_ALGO_SHA256, 8 words):
+// base64 of its bytes -- x-amz-checksum-sha1 / -sha256 of a part or a single-PUT object.
+inline std::string checksum_text(const std::vector<uint32_t>& digest, int algo = S3H_ALGO_SHA1) {
+  const size_t words = algo == S3H_ALGO_SHA256 ? 8 : 5;
+  if (digest.size() != words) throw std::invalid_argument("checksum_text: one digest expected");
+  char out[S3H_DIGEST_CHECKSUM_MAX];
+  sha256::batch_check(s3h_digest_checksum_text(algo, digest.data(), 1, 0, out, sizeof out));
+  return out;
+}
+
+// S3's COMPOSITE checksum of a multipart object from its parts' digests in part order:
+// base64 of the same hash over the raw digests concatenated, then "-n".
+inline std::string composite_checksum_text(const std::vector<uint32_t>& part_digests,
+                                           int algo = S3H_ALGO_SHA1) {
+  const size_t words = algo == S3H_ALGO_SHA256 ? 8 : 5;
+  if (part_digests.empty() || part_digests.size() % words)
+    throw std::invalid_argument("composite_checksum_text: need n x digest words");
+  char out[S3H_DIGEST_CHECKSUM_MAX];
+  sha256::batch_check(s3h_digest_checksum_text(algo, part_digests.data(), part_digests.size() / words,
+                                               1, out, sizeof out));
+  return out;
+}
+
+}  // namespace sha1

@@ -61,11 +61,16 @@ C_ABI_SYMBOLS = (
     "s3h_crc64nvme_verify_batch_device", "s3h_cpu_crc64nvme", "s3h_crc64nvme_combine",
     "s3h_crc64nvme_object", "s3h_checksum64_text", "s3h_crc64nvme_batch_host",
     "s3h_sha256_crc64nvme_batch_host", "s3h_sha256_crc64nvme_file_parts",
+    # SHA-1
+    "s3h_sha1_batch_device", "s3h_sha1_batch_host", "s3h_sha1_file_parts",
+    "s3h_sha256_sha1_batch_host", "s3h_sha256_sha1_file_parts", "s3h_cpu_sha1",
+    "s3h_digest_checksum_text",
 )
 CRC32C, CRC32 = 0, 1
 CRC64NVME = "crc64nvme"  # not an enum s3h_crc: the checksum has entry points of its own
 CRC_IDS = {"crc32c": CRC32C, "crc32": CRC32}
 CHECKSUM_MAX = 32
+DIGEST_CHECKSUM_MAX = 64
 POLICY_IDS = {"throughput": 0, "efficiency": 1, "power": 2}
 POLICY_NAMES = {v: k for k, v in POLICY_IDS.items()}
 SOURCE_IDS = {"pinned": 0, "pageable": 1, "file": 2}
@@ -136,9 +141,9 @@ class HostNuma(ctypes.Structure):
                 ("threads_node", ctypes.c_int), ("copy_threads", ctypes.c_int)]
 
 
-ALGO_SHA256, ALGO_MD5 = 0, 1
-ALGO_IDS = {"sha256": ALGO_SHA256, "md5": ALGO_MD5}
-DIGEST_WORDS = {ALGO_SHA256: 8, ALGO_MD5: 4}
+ALGO_SHA256, ALGO_MD5, ALGO_SHA1 = 0, 1, 2
+ALGO_IDS = {"sha256": ALGO_SHA256, "md5": ALGO_MD5, "sha1": ALGO_SHA1}
+DIGEST_WORDS = {ALGO_SHA256: 8, ALGO_MD5: 4, ALGO_SHA1: 5}
 # the lib/hash drop-in (C++ mangled names identical to the reference's libs3client.a)
 CXX_DROPIN_SYMBOLS = (
     "_ZN6sha2566sha256EPKhmPj",          # sha256::sha256(const uint8_t*, size_t, uint32_t*)
@@ -231,7 +236,7 @@ def lib() -> ctypes.CDLL:
             L.s3h_plan_dual_solo.argtypes = [ctypes.c_void_p, u32p]
             L.s3h_sha256_batch_device.argtypes = [ctypes.c_int, ctypes.c_void_p, u64p, u64p,
                                                   ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
-            for name in ("s3h_sha256_batch_host", "s3h_md5_batch_host"):
+            for name in ("s3h_sha256_batch_host", "s3h_md5_batch_host", "s3h_sha1_batch_host"):
                 getattr(L, name).argtypes = [ctypes.POINTER(ctypes.c_void_p), u64p,
                                              ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int,
                                              ctypes.c_uint64]
@@ -399,6 +404,14 @@ def lib() -> ctypes.CDLL:
                                          u32p]
             L.s3h_checksum_text.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
                                             ctypes.c_int, ctypes.c_char_p, ctypes.c_uint64]
+            L.s3h_sha1_batch_device.argtypes = L.s3h_md5_batch_device.argtypes
+            L.s3h_sha1_file_parts.argtypes = L.s3h_sha256_file_parts.argtypes
+            L.s3h_sha256_sha1_batch_host.argtypes = L.s3h_sha256_md5_batch_host.argtypes
+            L.s3h_sha256_sha1_file_parts.argtypes = L.s3h_sha256_md5_file_parts.argtypes
+            L.s3h_cpu_sha1.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
+            L.s3h_cpu_sha1.restype = None
+            L.s3h_digest_checksum_text.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
+                                                   ctypes.c_int, ctypes.c_char_p, ctypes.c_uint64]
             _lib = L
     return _lib
 

@@ -26,6 +26,11 @@
 #ifndef S3H_EXP_MD5_BPS
 #define S3H_EXP_MD5_BPS 4  // MD5 producer/consumer kernel: blocks per producer step
 #endif
+#ifndef S3H_EXP_SHA1_BPS
+// SHA-1 producer/consumer kernel: blocks per producer step while the grid fits one workgroup
+// per CU (40 KiB of LDS per block of the step); 1: the 1-block form for every grid
+#define S3H_EXP_SHA1_BPS 2
+#endif
 #ifndef S3H_EXP_MD5_ROLL
 #define S3H_EXP_MD5_ROLL 1  // MD5 consumer: the rolling fused step (0: the chunked one)
 #endif
@@ -97,6 +102,7 @@ static_assert(S3H_EXP_SKEW_BPS_NC2 == 8, "product build: S3H_EXP_SKEW_BPS_NC2 mu
 static_assert(S3H_EXP_PRODUCER_ROLLED == 0, "product build: unrolled skew producer");
 static_assert(S3H_EXP_MD5_SELF_DEPTH == 4, "product build: self-fed MD5 loads 4 blocks ahead");
 static_assert(S3H_EXP_MD5_BPS == 4, "product build: MD5 kernel with 4-block producer steps");
+static_assert(S3H_EXP_SHA1_BPS == 2, "product build: SHA-1 kernel with 2-block producer steps");
 static_assert(S3H_EXP_MD5_ROLL == 1, "product build: rolling MD5 row reads");
 static_assert(S3H_EXP_MD5_PSETS == 2, "product build: two MD5 producer register sets");
 static_assert(S3H_EXP_MD5_PSETS1 == 3, "product build: three sets for 1-block MD5 steps");

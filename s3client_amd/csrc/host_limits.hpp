@@ -16,12 +16,13 @@ constexpr int kAlgoCrc64Nvme = kAlgoCrcBase + 2;
 inline bool is_crc(int algo) { return algo == kAlgoCrc32c || algo == kAlgoCrc32 || algo == kAlgoCrc64Nvme; }
 inline int crc_of(int algo) { return algo - kAlgoCrcBase; }  // the CRC plan's id of a CRC algorithm
 
-// digest words per part: SHA-256 8, MD5 4, a 32-bit CRC 1, CRC-64/NVME 2
+// digest words per part: SHA-256 8, MD5 4, SHA-1 5, a 32-bit CRC 1, CRC-64/NVME 2
 inline uint32_t digest_words(int algo) {
-  return algo == S3H_ALGO_MD5 ? 4u : algo == kAlgoCrc64Nvme ? 2u : is_crc(algo) ? 1u : 8u;
+  return algo == S3H_ALGO_MD5 ? 4u : algo == S3H_ALGO_SHA1 ? 5u : algo == kAlgoCrc64Nvme ? 2u
+         : is_crc(algo) ? 1u : 8u;
 }
 
-// algorithms one host-path call computes: SHA-256, MD5 or a CRC alone, or two of them
+// algorithms one host-path call computes: SHA-256, MD5, SHA-1 or a CRC alone, or two of them
 constexpr int kHostMaxAlgo = 2;
 constexpr int kHostRing = 3;     // HBM ring slots / pinned staging slots
 

@@ -7,7 +7,7 @@
 // bytes, one copy stream and one hash stream per algorithm; slice k of every part is copied
 // while slice k-1 is hashed by a resumable launch (sha256_stream semantics, lib/hash/
 // sha256.cpp:84-144).  Many small parts go in groups of whole parts instead (run_host_groups).
-// An algorithm is SHA-256, MD5 or a CRC (host_limits.hpp is_crc): a CRC's "plan" is a CRC plan
+// An algorithm is SHA-256, MD5, SHA-1 or a CRC (host_limits.hpp is_crc): a CRC's "plan" is a CRC plan
 // and its resumable launch s3h_crc_plan_launch_range's, so SHA-256 and the x-amz-checksum-crc32c
 // / -crc32 / -crc64nvme value of a part come out of one pass over the host link.
 #include <fcntl.h>
@@ -942,6 +942,23 @@ int s3h_sha256_md5_batch_host(const uint8_t* const* parts, const uint64_t* lengt
   return batch_host(algos, 2, src, lengths, n, out, ndevices, slice_bytes);
 }
 
+int s3h_sha1_batch_host(const uint8_t* const* parts, const uint64_t* lengths, uint64_t n,
+                        uint32_t* digests, int ndevices, uint64_t slice_bytes) {
+  return batch_host(S3H_ALGO_SHA1, parts, lengths, n, digests, ndevices, slice_bytes);
+}
+
+// SHA-256 + SHA-1: no fused grid (plan.cpp dual_mode), so each plan runs on its own hash stream.
+int s3h_sha256_sha1_batch_host(const uint8_t* const* parts, const uint64_t* lengths, uint64_t n,
+                               uint32_t* sha256_digests, uint32_t* sha1_digests, int ndevices,
+                               uint64_t slice_bytes) {
+  static const int algos[2] = {S3H_ALGO_SHA256, S3H_ALGO_SHA1};
+  uint32_t* const out[2] = {sha256_digests, sha1_digests};
+  if (!parts) return fail(S3H_EINVAL, "batch_host: null parts");
+  PartSource src;
+  src.parts = parts;
+  return batch_host(algos, 2, src, lengths, n, out, ndevices, slice_bytes);
+}
+
 int s3h_sha256_batch_host_on(const uint8_t* const* parts, const uint64_t* lengths, uint64_t n,
                              uint32_t* digests, const int* devices, int ndevices,
                              uint64_t slice_bytes) {
@@ -973,6 +990,21 @@ int s3h_sha256_md5_file_parts(const char* path, const uint64_t* offsets, const u
                               int ndevices, uint64_t slice_bytes) {
   static const int algos[2] = {S3H_ALGO_SHA256, S3H_ALGO_MD5};
   uint32_t* const out[2] = {sha256_digests, md5_digests};
+  return file_parts(algos, 2, path, offsets, lengths, n, out, ndevices, slice_bytes);
+}
+
+int s3h_sha1_file_parts(const char* path, const uint64_t* offsets, const uint64_t* lengths,
+                        uint64_t n, uint32_t* digests, int ndevices, uint64_t slice_bytes) {
+  static const int algo = S3H_ALGO_SHA1;
+  uint32_t* const out[1] = {digests};
+  return file_parts(&algo, 1, path, offsets, lengths, n, out, ndevices, slice_bytes);
+}
+
+int s3h_sha256_sha1_file_parts(const char* path, const uint64_t* offsets, const uint64_t* lengths,
+                               uint64_t n, uint32_t* sha256_digests, uint32_t* sha1_digests,
+                               int ndevices, uint64_t slice_bytes) {
+  static const int algos[2] = {S3H_ALGO_SHA256, S3H_ALGO_SHA1};
+  uint32_t* const out[2] = {sha256_digests, sha1_digests};
   return file_parts(algos, 2, path, offsets, lengths, n, out, ndevices, slice_bytes);
 }
 
@@ -1046,7 +1078,7 @@ int s3h_verify_batch_host(int algo, const uint8_t* const* parts, const uint64_t*
                           uint64_t n, const uint32_t* expected, uint8_t* mismatch,
                           uint64_t* mismatches, int ndevices) {
   if (!expected || !mismatch || !mismatches) return fail(S3H_EINVAL, "verify: null argument");
-  if (algo != S3H_ALGO_SHA256 && algo != S3H_ALGO_MD5)
+  if (algo != S3H_ALGO_SHA256 && algo != S3H_ALGO_MD5 && algo != S3H_ALGO_SHA1)
     return fail(S3H_EINVAL, "verify: unknown algorithm %d", algo);
   const uint32_t dw = digest_words(algo);
   std::vector<uint32_t> got(n * dw);

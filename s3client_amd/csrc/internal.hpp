@@ -3,7 +3,7 @@
 // unit with device code), pinned host memory and device placement (pinned.cpp), and the
 // stream units' hooks.  The C-ABI itself is include/s3hash.h.
 //
-//   launch.hip    sha256_kernels.hip + crc32_kernels.hip + the hipLaunchKernelGGL calls (device code)
+//   launch.hip    sha256_kernels.hip + sha1_kernels.hip + crc32_kernels.hip + the hipLaunchKernelGGL calls (device code)
 //   plan.cpp      plans: kernel choice, slot sorting, launches, error words; device-resident C-ABI
 //   pinned.cpp    NUMA-placed pinned host memory, device placement, s3h_host_alloc / _numa
 //   host_path.cpp host-resident pipeline (slices, groups), per-device contexts, the merge queue
@@ -154,7 +154,7 @@ hipError_t launch_plan_kernel(const s3h_plan_s* P, int cus, uint64_t range_block
 hipError_t launch_dual_kernel(DualMode mode, const s3h_plan_s* S, const s3h_plan_s* M,
                               const s3h::LaunchArgs& A, const s3h::LaunchArgs& B, uint64_t* progress,
                               uint32_t epoch, hipStream_t s);
-hipError_t launch_stream_init(uint32_t* state, uint64_t n, int md5, hipStream_t s);
+hipError_t launch_stream_init(uint32_t* state, uint64_t n, int algo, hipStream_t s);
 hipError_t launch_stream_splice(const uint8_t* base, const s3h::SpliceJob* jobs, uint8_t* carry,
                                 uint8_t* head, uint64_t n, hipStream_t s);
 hipError_t launch_compare_digests(const uint32_t* got, const uint32_t* want, uint64_t n,

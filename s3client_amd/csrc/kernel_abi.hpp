@@ -84,6 +84,10 @@ constexpr int kQuadChainsPerWave = 8;    // skew / quad: 8 chains per consumer w
 // MD5 kernel: kMd5Bps-block producer steps (128 KiB of LDS, one workgroup per CU) while the
 // grid fits one workgroup per CU (<= 64 x CUs parts); 1-block steps (32 KiB) beyond.
 constexpr int kMd5Bps = S3H_EXP_MD5_BPS;
+// SHA-1 kernel: kSha1Bps-block producer steps (80 KiB of LDS) while the grid fits one workgroup
+// per CU (<= 64 x CUs parts); 1-block steps (40 KiB, up to four workgroups per CU) beyond.
+constexpr int kSha1Bps = S3H_EXP_SHA1_BPS;
+static_assert(kSha1Bps >= 1 && kSha1Bps <= 3, "SHA-1 steps: 40 KiB of LDS per block, 160 KiB per CU");
 
 // ------------------------------------------------------------- multi-object streams
 // Carry bookkeeping of one s3h_stream update, one thread per message (<= 127 bytes moved):

@@ -1,10 +1,11 @@
 // launch.hip -- the only translation unit with device code: the gfx950 kernels of
-// sha256_kernels.hip, crc32_kernels.hip and crc64_kernels.hip and the launches that pick among them.  Everything around the launches --
+// sha256_kernels.hip, sha1_kernels.hip, crc32_kernels.hip and crc64_kernels.hip and the launches that pick among them.  Everything around the launches --
 // plans, the host pipeline, streams, routing -- is host C++ in the other units (internal.hpp).
 #include <hip/hip_runtime.h>
 
 #include "internal.hpp"
 #include "sha256_kernels.hip"
+#include "sha1_kernels.hip"
 #include "crc32_kernels.hip"
 #include "crc64_kernels.hip"
 
@@ -24,6 +25,11 @@ hipError_t launch_plan_kernel(const s3h_plan_s* P, int cus, uint64_t range, cons
                        stream, A);
   else if (P->algo == S3H_ALGO_MD5)  // more workgroups than CUs: the 32 KiB form, several per CU
     hipLaunchKernelGGL(s3h::md5_pc_kernel<1>, dim3(P->grid), dim3(s3h::kPcThreads), 0, stream, A);
+  else if (P->algo == S3H_ALGO_SHA1 && s3h::kSha1Bps > 1 && P->grid <= uint64_t(cus))
+    hipLaunchKernelGGL(s3h::sha1_pc_kernel<s3h::kSha1Bps>, dim3(P->grid), dim3(s3h::kPcThreads), 0,
+                       stream, A);
+  else if (P->algo == S3H_ALGO_SHA1)  // more workgroups than CUs: the 40 KiB form, several per CU
+    hipLaunchKernelGGL(s3h::sha1_pc_kernel<1>, dim3(P->grid), dim3(s3h::kPcThreads), 0, stream, A);
   // The skew kernel counts a launch's blocks in 32 bits: a range of 2^31 blocks (128 GiB of
   // one part) or more runs on the quad kernel (same slots and state, 64-bit counters).  The
   // quad kernel reads its workgroup's first slot before any bounds check, so its grid is the
@@ -81,8 +87,8 @@ hipError_t launch_dual_kernel(DualMode mode, const s3h_plan_s* S, const s3h_plan
   return hipGetLastError();
 }
 
-hipError_t launch_stream_init(uint32_t* state, uint64_t n, int md5, hipStream_t s) {
-  hipLaunchKernelGGL(s3h::stream_init_kernel, dim3(uint32_t((n + 255) / 256)), dim3(256), 0, s, state, n, md5);
+hipError_t launch_stream_init(uint32_t* state, uint64_t n, int algo, hipStream_t s) {
+  hipLaunchKernelGGL(s3h::stream_init_kernel, dim3(uint32_t((n + 255) / 256)), dim3(256), 0, s, state, n, algo);
   return hipGetLastError();
 }
 

@@ -127,6 +127,7 @@ std::atomic<int> g_kernel_policy{[] {
 
 int resolve_kernel(int algo, uint64_t n, int kernel, uint64_t cus, int device) {
   if (algo == S3H_ALGO_MD5) return S3H_KERNEL_PC;  // MD5 has one kernel (4 VALU per step)
+  if (algo == S3H_ALGO_SHA1) return S3H_KERNEL_PC;  // SHA-1 too (5 VALU per round)
   if (kernel != S3H_KERNEL_AUTO) return kernel;
   const int policy = g_kernel_policy.load();
   const bool efficient = policy == S3H_POLICY_EFFICIENCY ||
@@ -141,12 +142,14 @@ int resolve_kernel(int algo, uint64_t n, int kernel, uint64_t cus, int device) {
 }
 
 int check_plan_args(int device, int algo, uint64_t n, int kernel) {
-  if (algo != S3H_ALGO_SHA256 && algo != S3H_ALGO_MD5)
+  if (algo != S3H_ALGO_SHA256 && algo != S3H_ALGO_MD5 && algo != S3H_ALGO_SHA1)
     return fail(S3H_EINVAL, "plan: unknown algorithm %d", algo);
   if (n == 0 || n > kMaxParts)
     return fail(S3H_EINVAL, "plan: need 0 < n <= 2^31 (n=%llu)", (unsigned long long)n);
   if (algo == S3H_ALGO_MD5 && kernel != S3H_KERNEL_AUTO && kernel != S3H_KERNEL_PC)
     return fail(S3H_EINVAL, "plan: MD5 supports only the producer/consumer kernel");
+  if (algo == S3H_ALGO_SHA1 && kernel != S3H_KERNEL_AUTO && kernel != S3H_KERNEL_PC)
+    return fail(S3H_EINVAL, "plan: SHA-1 supports only the producer/consumer kernel");
   if (kernel < S3H_KERNEL_AUTO || kernel > S3H_KERNEL_SKEWS)
     return fail(S3H_EINVAL, "plan: unknown kernel %d", kernel);
   return check_device(device);
@@ -177,6 +180,7 @@ s3h::LaunchArgs make_args(s3h_plan_s* P, const void* d_base, uint32_t* d_digests
 const char* kernel_name(const s3h_plan_s* P) {
   static const char* const names[] = {"auto", "lane", "pc", "pair", "quad", "skew", "skewp", "skews"};
   if (P->algo == S3H_ALGO_MD5) return "md5";
+  if (P->algo == S3H_ALGO_SHA1) return "sha1";
   return P->kernel >= 0 && P->kernel <= S3H_KERNEL_SKEWS ? names[P->kernel] : "?";
 }
 
@@ -488,7 +492,8 @@ namespace {
 
 // Consumer waves (= groups) of a skew/skewp grid; 0 for the kernels without a clock probe.
 uint32_t consumer_groups(const s3h_plan_s* P) {
-  if (P->algo == S3H_ALGO_MD5) return P->grid;  // md5_pc_kernel: one consumer wave per workgroup
+  // md5_pc_kernel, sha1_pc_kernel: one consumer wave per workgroup
+  if (P->algo == S3H_ALGO_MD5 || P->algo == S3H_ALGO_SHA1) return P->grid;
   return (P->kernel == S3H_KERNEL_SKEW && P->quad_waves == 2) || P->kernel == S3H_KERNEL_SKEWS
              ? uint32_t((P->n + 7) / 8)
          : P->kernel == S3H_KERNEL_SKEW || P->kernel == S3H_KERNEL_SKEWP ? P->grid
@@ -654,6 +659,11 @@ int s3h_sha256_batch_device(int device, const void* d_base, const uint64_t* offs
 int s3h_md5_batch_device(int device, const void* d_base, const uint64_t* offsets,
                          const uint64_t* lengths, uint64_t n, uint32_t* d_digests, void* stream) {
   return batch_device(device, S3H_ALGO_MD5, d_base, offsets, lengths, n, d_digests, stream);
+}
+
+int s3h_sha1_batch_device(int device, const void* d_base, const uint64_t* offsets,
+                          const uint64_t* lengths, uint64_t n, uint32_t* d_digests, void* stream) {
+  return batch_device(device, S3H_ALGO_SHA1, d_base, offsets, lengths, n, d_digests, stream);
 }
 
 int s3h_sha256_md5_batch_device(int device, const void* d_base, const uint64_t* offsets,

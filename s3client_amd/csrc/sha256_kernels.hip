@@ -29,6 +29,7 @@
 //   md5_pc_kernel<4 | 1>        MD5 (Content-MD5 / ETag): 4-block producer steps
 //       while the grid fits one workgroup per CU, 1-block steps (32 KiB LDS) beyond.
 //   sha256_md5_*_kernel         both digests of every part from one grid (capi.hip dual).
+//   sha1_pc_kernel<2 | 1>       SHA-1 (x-amz-checksum-sha1): sha1_kernels.hip.
 // In the producer/consumer kernels the producer wave streams each part's 64-byte blocks from
 // HBM (cached loads), aligns and byte-swaps them (one v_perm per word), synthesises the
 // padding, expands the message schedule and writes W[t]+K[t] into an LDS double buffer; the
@@ -2308,13 +2309,16 @@ __global__ __launch_bounds__(256) void stream_splice_kernel(const uint8_t* base,
     for (uint32_t k = 0; k < j.r; ++k) cy[k] = base[j.tail + k];
 }
 
-// Chaining state of n empty messages (8-word stride for both algorithms).
-__global__ __launch_bounds__(256) void stream_init_kernel(uint32_t* state, uint64_t n, int md5) {
+// Chaining state of n empty messages (8-word stride for every algorithm; `algo`: enum s3h_algo).
+__global__ __launch_bounds__(256) void stream_init_kernel(uint32_t* state, uint64_t n, int algo) {
   const uint64_t i = uint64_t(blockIdx.x) * 256u + threadIdx.x;
   if (i >= n) return;
   uint4* s = reinterpret_cast<uint4*>(state + 8 * i);
-  if (md5) {
+  if (algo == 1) {  // MD5
     s[0] = make_uint4(0x67452301u, 0xefcdab89u, 0x98badcfeu, 0x10325476u);
+  } else if (algo == 2) {  // SHA-1: five words
+    s[0] = make_uint4(0x67452301u, 0xefcdab89u, 0x98badcfeu, 0x10325476u);
+    s[1] = make_uint4(0xc3d2e1f0u, 0u, 0u, 0u);
   } else {
     s[0] = make_uint4(0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au);
     s[1] = make_uint4(0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u);

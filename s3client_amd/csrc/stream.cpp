@@ -167,7 +167,7 @@ int stream_reset(s3h_stream_s* S, hipStream_t s) {
   std::fill(S->total.begin(), S->total.end(), 0);
   std::fill(S->carry.begin(), S->carry.end(), 0u);
   (void)hipGetLastError();
-  HIP_TRY(launch_stream_init(S->d_state, S->n, int(S->algo == S3H_ALGO_MD5), s));
+  HIP_TRY(launch_stream_init(S->d_state, S->n, S->algo, s));
   return S3H_OK;
 }
 

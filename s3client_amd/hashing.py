@@ -10,6 +10,8 @@ hashes (lib/src/upload.cpp:89-110 -> S3Api::UploadFilePart(..., payloadHash)):
   * ``sha256_batch_host``               -- parts in host memory, sharded over GPUs
   * ``sha256_md5_batch_{host,device}``  -- both digests (x-amz-content-sha256 + Content-MD5)
                                            from one pass over the parts
+  * ``sha1_batch_{device,host}``, ``sha256_sha1_batch_host``, ``Plan(..., algo="sha1")``,
+    ``Stream(algo="sha1")``             -- SHA-1 (x-amz-checksum-sha1), 5 words per part
 
 Device memory, streams and events come from PyTorch (plumbing only); all hashing is done by
 the HIP kernels in s3client_amd/csrc.  Nothing here falls back to the CPU for a batch.
@@ -540,6 +542,76 @@ def checksum_text(part_crcs, algo: str | int = "crc32c", composite: bool = False
     out = ctypes.create_string_buffer(_native.CHECKSUM_MAX)
     check(lib().s3h_checksum_text(_crc_id(algo), ctypes.c_void_p(w.ctypes.data), w.size,
                                   int(bool(composite)), out, len(out)))
+    return out.value.decode()
+
+
+# ------------------------------------------------------------------ SHA-1 checksum
+def sha1_batch_device(data, offsets, lengths, device: int | None = None, stream=None):
+    """Batched SHA-1 (x-amz-checksum-sha1) of device-resident parts: (n, 5) int32 device tensor,
+    word i = bswap32(H_i) (the 20 bytes of a row are the canonical digest)."""
+    return sha256_batch_device(data, offsets, lengths, device, "auto", stream, algo="sha1")
+
+
+def sha1_batch_host(parts: Sequence, ndevices: int = 0, slice_bytes: int = 0) -> np.ndarray:
+    """Batched SHA-1 of host-resident parts on the GPUs (s3h_sha1_batch_host): (n, 5) uint32."""
+    return _host_batch(lib().s3h_sha1_batch_host, 5, parts, ndevices, slice_bytes)
+
+
+def sha256_sha1_batch_host(parts: Sequence, ndevices: int = 0,
+                           slice_bytes: int = 0) -> tuple[np.ndarray, np.ndarray]:
+    """SHA-256 (n, 8) and SHA-1 (n, 5) uint32 digests of host-resident parts, each part crossing
+    PCIe once (s3h_sha256_sha1_batch_host)."""
+    arrs, ptrs, lens = _host_parts(parts)
+    n = len(arrs)
+    sha = np.zeros((n, DIGEST_WORDS), dtype=np.uint32)
+    s1 = np.zeros((n, 5), dtype=np.uint32)
+    check(lib().s3h_sha256_sha1_batch_host(ptrs, _p64(lens), n, sha.ctypes.data, s1.ctypes.data,
+                                           ndevices, slice_bytes))
+    return sha, s1
+
+
+def sha1_file_parts(path: str, offsets, lengths, ndevices: int = 0, slice_bytes: int = 0) -> np.ndarray:
+    """SHA-1 of file ranges on the GPU (s3h_sha1_file_parts): (n, 5) uint32."""
+    offs, lens = _u64(offsets), _u64(lengths)
+    if offs.shape != lens.shape or offs.ndim != 1 or offs.size == 0:
+        raise ValueError("offsets and lengths must be 1-D, equal length and non-empty")
+    out = np.zeros((offs.size, 5), dtype=np.uint32)
+    check(lib().s3h_sha1_file_parts(os.fsencode(path), _p64(offs), _p64(lens), offs.size,
+                                    out.ctypes.data, ndevices, slice_bytes))
+    return out
+
+
+def sha256_sha1_file_parts(path: str, offsets, lengths, ndevices: int = 0,
+                           slice_bytes: int = 0) -> tuple[np.ndarray, np.ndarray]:
+    """SHA-256 (n, 8) and SHA-1 (n, 5) uint32 digests of file ranges, each slice read once
+    (s3h_sha256_sha1_file_parts)."""
+    offs, lens = _u64(offsets), _u64(lengths)
+    if offs.shape != lens.shape or offs.ndim != 1 or offs.size == 0:
+        raise ValueError("offsets and lengths must be 1-D, equal length and non-empty")
+    sha = np.zeros((offs.size, DIGEST_WORDS), dtype=np.uint32)
+    s1 = np.zeros((offs.size, 5), dtype=np.uint32)
+    check(lib().s3h_sha256_sha1_file_parts(os.fsencode(path), _p64(offs), _p64(lens), offs.size,
+                                           sha.ctypes.data, s1.ctypes.data, ndevices, slice_bytes))
+    return sha, s1
+
+
+def sha1(data: bytes) -> np.ndarray:
+    """SHA-1 on the CPU (s3h_cpu_sha1, single message): 5 words, hash[i] = bswap32(H_i)."""
+    b = bytes(data)
+    out = np.zeros(5, dtype=np.uint32)
+    lib().s3h_cpu_sha1(b, len(b), out.ctypes.data)
+    return out
+
+
+def digest_checksum_text(digests, algo: str = "sha1", composite: bool = False) -> str:
+    """Header text of a digest checksum (s3h_digest_checksum_text), ``algo`` "sha1" or "sha256":
+    base64 of one digest (x-amz-checksum-sha1 / -sha256 of a part or a single-PUT object), or
+    with ``composite`` S3's COMPOSITE form of the parts' digests, "<base64>-<n>"."""
+    a = _native.ALGO_IDS[algo]
+    w = np.ascontiguousarray(digests).astype(np.uint32, copy=False).reshape(-1, _native.DIGEST_WORDS[a])
+    out = ctypes.create_string_buffer(_native.DIGEST_CHECKSUM_MAX)
+    check(lib().s3h_digest_checksum_text(a, ctypes.c_void_p(w.ctypes.data), w.shape[0],
+                                         int(bool(composite)), out, len(out)))
     return out.value.decode()
 
 

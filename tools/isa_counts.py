@@ -32,6 +32,8 @@ KERNELS = {
     "skewp": ("_ZN3s3h18sha256_skew_kernelILi1ELb1EEEvNS_10LaunchArgsE", 4),
     "skews": ("_ZN3s3h25sha256_skew_shared_kernelENS_10LaunchArgsE", 8),
     "md5-pc": ("_ZN3s3h13md5_pc_kernelILi4EEEvNS_10LaunchArgsE", 4),  # S3H_EXP_MD5_BPS
+    "sha1-pc": ("_ZN3s3h14sha1_pc_kernelILi2EEEvNS_10LaunchArgsE", 2),  # S3H_EXP_SHA1_BPS
+    "sha1-pc1": ("_ZN3s3h14sha1_pc_kernelILi1EEEvNS_10LaunchArgsE", 1),
 }
 # every kernel a plan can launch (code hashes) and the flag-synchronised ones among them, whose
 # timed-out waits must reach the device error word (sha256_kernels.hip flag_wait_ge)
@@ -59,6 +61,8 @@ ALL_KERNELS = {
     "crc64_parts": "_ZN3s3h18crc64_parts_kernelENS_9Crc64ArgsE",
     "crc64_range_pieces": "_ZN3s3h25crc64_range_pieces_kernelENS_9Crc64ArgsE",
     "crc64_range_parts": "_ZN3s3h24crc64_range_parts_kernelENS_9Crc64ArgsE",
+    # SHA-1 (sha1_kernels.hip)
+    "sha1-pc": KERNELS["sha1-pc"][0], "sha1-pc1": KERNELS["sha1-pc1"][0],
 }
 FLAG_KERNELS = ("skew_nc2", "skews", "dual_group", "dual_group_skew", "dual_group_mixed")
 ERR_STORE = re.compile(r"^\t(global|flat|buffer)_atomic_or\b")
@@ -138,10 +142,12 @@ def main(lib, dst, dis_out=None):
         cand = [(n, o) for n, o in loops(function_body(lines, sym))
                 if not any(x.startswith(("ds_write_b128", "global_load", "global_store", "buffer_",
                                          "flat_")) for x in o)]
-        if name == "md5-pc":
+        if name in ("md5-pc", "sha1-pc", "sha1-pc1"):
             # the consumer's fast loop (every chain live: no per-lane select) comes first in
             # the code, before the ragged-tail loop that is a few selects longer
-            cand = [x for x in cand if sum(o.startswith("v_") for o in x[1]) >= 256 * bps]
+            # (MD5: 4 VALU x 64 steps per block; SHA-1: 5 VALU x 80 rounds)
+            floor = 256 if name == "md5-pc" else 400
+            cand = [x for x in cand if sum(o.startswith("v_") for o in x[1]) >= floor * bps]
             label, ops = cand[0]
         else:
             label, ops = max(cand, key=lambda x: len(x[1]))
