@@ -19,6 +19,10 @@
  *       _file_parts, S3H_ALGO_SHA1 in s3h_plan_create_ex / s3h_stream_create / s3h_verify_*,
  *       s3h_cpu_sha1, s3h_digest_checksum_text  -- x-amz-checksum-sha1 (lib/hash has no SHA-1;
  *       FIPS 180-4): 5 words per part in the same word convention.
+ *   s3h_sigv4_signing_key, s3h_chunk_sign_ctx_*, s3h_chunk_plan_*, s3h_chunk_sign_batch_device /
+ *       _host, s3h_cpu_chunk_signatures, s3h_chunk_header_text  -- aws-chunked bodies signed per
+ *       chunk (STREAMING-AWS4-HMAC-SHA256-PAYLOAD), which the reference's signer does not
+ *       produce (lib/src/aws_sign.cpp signs whole payloads): chunk hashes and the HMAC chain.
  *
  * Digest layout (every entry point): 8 uint32 words per part with word i = bswap32(H_i),
  * exactly lib/hash's `to_little` output (sha256.h:103-106); on little-endian hosts the 32
@@ -42,7 +46,9 @@ extern "C" {
  * then CRC-64/NVME (s3h_crc64nvme_*, s3h_cpu_crc64nvme, s3h_checksum64_text,
  * s3h_sha256_crc64nvme_*), then SHA-1 (S3H_ALGO_SHA1 for plans, streams and verification,
  * s3h_sha1_batch_device, s3h_sha1_batch_host, s3h_sha1_file_parts, s3h_sha256_sha1_batch_host,
- * s3h_sha256_sha1_file_parts, s3h_cpu_sha1, s3h_digest_checksum_text). */
+ * s3h_sha256_sha1_file_parts, s3h_cpu_sha1, s3h_digest_checksum_text), then SigV4 chunk-signed
+ * uploads (s3h_sigv4_signing_key, s3h_chunk_sign_ctx_*, s3h_cpu_chunk_signatures,
+ * s3h_chunk_header_text, s3h_chunk_geometry, s3h_chunk_plan_*, s3h_chunk_sign_batch_device / _host). */
 #define S3H_API_VERSION 2
 
 enum s3h_status {
@@ -703,6 +709,103 @@ void s3h_cpu_sha1(const uint8_t *data, uint64_t length, uint32_t hash[5]);
 #define S3H_DIGEST_CHECKSUM_MAX 64
 int s3h_digest_checksum_text(int algo, const uint32_t *digests, uint64_t n, int composite,
                              char *out, uint64_t out_len);
+
+/* ---------------------------------------------------------------- SigV4 chunk-signed uploads
+ * An aws-chunked body under x-amz-content-sha256: STREAMING-AWS4-HMAC-SHA256-PAYLOAD (what the
+ * AWS SDKs send when they stream a body over plain HTTP) needs no whole-part SHA-256: the part is
+ * cut into chunks of chunk_bytes (the last may be short; the server asks for >= 8 KiB, the SDKs
+ * use 64 KiB), each chunk is hashed on its own, and a chain of HMACs links them:
+ *   sig_i = HMAC-SHA256(signing_key, "AWS4-HMAC-SHA256-PAYLOAD\n" timestamp "\n"
+ *             date "/" region "/" service "/aws4_request\n" hex(sig_{i-1}) "\n"
+ *             hex(sha256("")) "\n" hex(sha256(chunk_i)))
+ * sig_0 being the seed: the signature of the request's headers (computed with the payload hash
+ * "STREAMING-AWS4-HMAC-SHA256-PAYLOAD").  A final chunk of 0 bytes closes the body, so a part of
+ * L bytes has ceil(L / chunk_bytes) data chunks and one signature more (an empty part: one).
+ * Signatures are stored like SHA-256 digests: 8 words each, word i = bswap32(H_i), the 32 raw
+ * bytes in memory; seeds likewise, one per part.  `signatures` arrays are part-major: part p's
+ * signatures follow part p-1's.  The chunk hashes are independent, so one large part fills the
+ * GPU; the chain of a part is serial and ~6 compressions per chunk.  Device-resident plans run
+ * it on the device behind the hash launch (stream-ordered, no host work between); the
+ * host-resident entry point runs it on the CPU, where the digests land anyway.  A device caller
+ * with a few long parts is better off hashing the chunks with an ordinary SHA-256 plan and
+ * calling s3h_cpu_chunk_signatures: one GPU lane walks a chain ~100x slower than one CPU core.
+ * The trailer variant (...-PAYLOAD-TRAILER) is not covered.  Added within API version 2. */
+typedef struct s3h_chunk_sign_ctx_s *s3h_chunk_sign_ctx_t;
+typedef struct s3h_chunk_plan_s *s3h_chunk_plan_t;
+/* signing_key = HMAC(HMAC(HMAC(HMAC("AWS4" + secret, date), region), service), "aws4_request")
+ * (NUL-terminated strings).  CPU. */
+int s3h_sigv4_signing_key(const char *secret, const char *date, const char *region,
+                          const char *service, uint8_t key[32]);
+/* The constant part of every chunk's string to sign, hashed once: timestamp "YYYYMMDDThhmmssZ"
+ * (16 bytes), date "YYYYMMDD" (8 bytes), region and service non-empty and together at most 190
+ * bytes (the prefix is 66 + |region| + |service| <= 256 bytes); S3H_EINVAL otherwise.  CPU; a
+ * context is immutable and may be used from any number of threads and launches at once. */
+int s3h_chunk_sign_ctx_create(const uint8_t key[32], const char *timestamp, const char *date,
+                              const char *region, const char *service, s3h_chunk_sign_ctx_t *out);
+int s3h_chunk_sign_ctx_destroy(s3h_chunk_sign_ctx_t ctx);
+/* The chain on the CPU over ready chunk digests: chunk_digests holds the data chunks' SHA-256
+ * digests (8 words each), part-major, data_chunks_per_part[p] of them for part p (the final
+ * chunk's hash is implied; chunk_digests may be null when there is no data chunk); seeds n x 8
+ * words; signatures receives sum(data_chunks_per_part[p] + 1) x 8 words.  Parts are spread over
+ * the host threads s3h_host_threads(1) reports. */
+int s3h_cpu_chunk_signatures(s3h_chunk_sign_ctx_t ctx, const uint32_t *chunk_digests,
+                             const uint64_t *data_chunks_per_part, uint64_t n, const uint32_t *seeds,
+                             uint32_t *signatures);
+/* The framing line an uploader writes before a chunk's bytes (and "\r\n" after them):
+ * "<chunk_len in hex>;chunk-signature=<64 hex>\r\n", NUL-terminated, out_len >=
+ * S3H_CHUNK_HEADER_MAX.  The body ends with the line of chunk_len 0 and a last "\r\n". */
+#define S3H_CHUNK_HEADER_MAX 104
+int s3h_chunk_header_text(uint64_t chunk_len, const uint32_t sig[8], char *out, uint64_t out_len);
+/* The chunk geometry of parts of `lengths` at chunk_bytes >= 1, without a device (pure host
+ * arithmetic, the rule the plans and the batch calls apply): per part its data chunks,
+ * ceil(length / chunk_bytes), and the index of its first signature in a part-major signatures
+ * array (n entries each), and for the batch the data chunks, the signatures (data chunks + n) and
+ * the longest part's data chunks.  Any output may be null.  S3H_EINVAL for chunk_bytes == 0,
+ * n == 0 or more than 2^31 parts or data chunks. */
+int s3h_chunk_geometry(const uint64_t *lengths, uint64_t n, uint64_t chunk_bytes,
+                       uint64_t *data_chunks_per_part, uint64_t *signature_offsets,
+                       uint64_t *data_chunks, uint64_t *signatures, uint64_t *max_chunks_per_part);
+/* Device-resident parts (offsets relative to a base pointer, as s3h_plan_create) cut into chunks
+ * of chunk_bytes >= 1: an S3H_ALGO_SHA256 plan over the chunks (S3H_KERNEL_AUTO) plus each part's
+ * chain record.  At most 2^31 data chunks in all; a batch without one (every part empty) is
+ * valid.  The plan owns the chunk digests: launch one plan on ONE stream at a time. */
+int s3h_chunk_plan_create(int device, const uint64_t *offsets, const uint64_t *lengths, uint64_t n,
+                          uint64_t chunk_bytes, s3h_chunk_plan_t *out);
+/* Asynchronous on `stream`: the chunk-hash launch, then the chain kernel.  d_seeds (n x 8 words)
+ * and d_signatures (signatures x 8 words, s3h_chunk_plan_info) are device pointers, 16-byte
+ * aligned; nothing behind the last signature is written.  The context is read during the call
+ * only.  As for s3h_plan_launch, call s3h_chunk_plan_status before using the signatures. */
+int s3h_chunk_plan_launch(s3h_chunk_plan_t plan, s3h_chunk_sign_ctx_t ctx, const void *d_base,
+                          const uint32_t *d_seeds, uint32_t *d_signatures, void *stream);
+/* The chain kernel alone, over data-chunk digests already on the device (d_chunk_digests: data
+ * chunks x 8 words, part-major in the plan's geometry, 16-byte aligned; may be null for a plan
+ * without a data chunk) -- for a caller that hashed the chunks itself.  Asynchronous on `stream`;
+ * it does not touch the plan's own digests, so it may run beside a launch of the plan. */
+int s3h_chunk_plan_chain(s3h_chunk_plan_t plan, s3h_chunk_sign_ctx_t ctx,
+                         const uint32_t *d_chunk_digests, const uint32_t *d_seeds,
+                         uint32_t *d_signatures, void *stream);
+/* s3h_plan_status of the chunk-hash plan (waits for `stream`): S3H_OK means the chunk digests,
+ * and so the signatures, of every launch since the last call were produced. */
+int s3h_chunk_plan_status(s3h_chunk_plan_t plan, void *stream);
+/* n parts, data chunks and signatures in all, the longest chain's data chunks, and the name of
+ * the chunk-hash kernel ("lane", "skew", ...; "none" without a data chunk) into kernel_name
+ * (NUL-terminated, truncated to len).  Any pointer may be null. */
+int s3h_chunk_plan_info(s3h_chunk_plan_t plan, uint64_t *n, uint64_t *data_chunks,
+                        uint64_t *signatures, uint64_t *max_chunks_per_part, char *kernel_name,
+                        int len);
+int s3h_chunk_plan_destroy(s3h_chunk_plan_t plan);
+/* One-shot, blocking: plan + launch + status + copy back.  d_base is a device pointer; seeds_host
+ * (n x 8 words) and signatures_host (sum(ceil(lengths[p] / chunk_bytes) + 1) x 8 words) are host
+ * memory. */
+int s3h_chunk_sign_batch_device(int device, s3h_chunk_sign_ctx_t ctx, const void *d_base,
+                                const uint64_t *offsets, const uint64_t *lengths, uint64_t n,
+                                uint64_t chunk_bytes, const uint32_t *seeds_host,
+                                uint32_t *signatures_host);
+/* Host-resident parts: the chunks go through s3h_sha256_batch_host as its parts (all visible
+ * devices, automatic slices), then the chain runs on the CPU.  Blocking. */
+int s3h_chunk_sign_batch_host(s3h_chunk_sign_ctx_t ctx, const uint8_t *const *parts,
+                              const uint64_t *lengths, uint64_t n, uint64_t chunk_bytes,
+                              const uint32_t *seeds, uint32_t *signatures);
 
 /* ---------------------------------------------------------------- synthetic inputs
  * Fill part i (at d_base + offsets[i], 8-B aligned, lengths[i] bytes) with generator

@@ -546,3 +546,121 @@ inline std::string composite_checksum_text(const std::vector<uint32_t>& part_dig
 }
 
 }  // namespace sha1
+
+// SigV4 chunk-signed uploads (aws-chunked bodies, STREAMING-AWS4-HMAC-SHA256-PAYLOAD): each part
+// cut into chunks, each chunk hashed on its own, one HMAC per chunk chained from the request's
+// seed signature.  Signatures and seeds are 8 words each in the SHA-256 digest layout (the 32
+// raw bytes in memory), part-major: a part's data-chunk signatures, then its final 0-byte
+// chunk's.
+namespace s3h {
+
+// SigV4 signing key of `secret` for a date "YYYYMMDD", a region and a service.
+inline std::vector<uint8_t> sigv4_signing_key(const std::string& secret, const std::string& date,
+                                              const std::string& region, const std::string& service = "s3") {
+  std::vector<uint8_t> key(32);
+  sha256::batch_check(s3h_sigv4_signing_key(secret.c_str(), date.c_str(), region.c_str(), service.c_str(),
+                                            key.data()));
+  return key;
+}
+
+// The constant part of every chunk's string to sign, hashed once (s3h_chunk_sign_ctx_create).
+class ChunkSignContext {
+ public:
+  ChunkSignContext(const std::vector<uint8_t>& key, const std::string& timestamp, const std::string& date,
+                   const std::string& region, const std::string& service = "s3") {
+    if (key.size() != 32) throw std::invalid_argument("ChunkSignContext: the signing key is 32 bytes");
+    sha256::batch_check(s3h_chunk_sign_ctx_create(key.data(), timestamp.c_str(), date.c_str(),
+                                                  region.c_str(), service.c_str(), &c_));
+  }
+  ~ChunkSignContext() { s3h_chunk_sign_ctx_destroy(c_); }
+  ChunkSignContext(const ChunkSignContext&) = delete;
+  ChunkSignContext& operator=(const ChunkSignContext&) = delete;
+  s3h_chunk_sign_ctx_t get() const { return c_; }
+
+  // The chains on the CPU over ready chunk digests (s3h_cpu_chunk_signatures): 8 words per data
+  // chunk, part-major, data_chunks_per_part[p] of them for part p; seeds 8 words per part.
+  std::vector<uint32_t> signatures(const std::vector<uint32_t>& chunk_digests,
+                                   const std::vector<uint64_t>& data_chunks_per_part,
+                                   const std::vector<uint32_t>& seeds) const {
+    uint64_t chunks = 0;
+    for (uint64_t c : data_chunks_per_part) chunks += c;
+    if (chunk_digests.size() != 8 * chunks || seeds.size() != 8 * data_chunks_per_part.size())
+      throw std::invalid_argument("ChunkSignContext: 8 words per data chunk and per seed");
+    std::vector<uint32_t> out(8 * (chunks + data_chunks_per_part.size()));
+    sha256::batch_check(s3h_cpu_chunk_signatures(c_, chunk_digests.data(), data_chunks_per_part.data(),
+                                                 data_chunks_per_part.size(), seeds.data(), out.data()));
+    return out;
+  }
+
+ private:
+  s3h_chunk_sign_ctx_t c_ = nullptr;
+};
+
+// Device-resident parts (at d_base + offsets[i]) cut into chunks of chunk_bytes: the chunk
+// hashes and the chains run on `stream` (s3h_chunk_plan_*).  One plan on one stream at a time.
+class ChunkSignPlan {
+ public:
+  ChunkSignPlan(int device, const std::vector<uint64_t>& offsets, const std::vector<uint64_t>& lengths,
+                uint64_t chunk_bytes) {
+    if (offsets.size() != lengths.size()) throw std::invalid_argument("offsets/lengths size mismatch");
+    sha256::batch_check(s3h_chunk_plan_create(device, offsets.data(), lengths.data(), offsets.size(),
+                                              chunk_bytes, &p_));
+    signature_offsets_.resize(lengths.size());
+    sha256::batch_check(s3h_chunk_geometry(lengths.data(), lengths.size(), chunk_bytes, nullptr,
+                                           signature_offsets_.data(), nullptr, &signatures_, nullptr));
+  }
+  ~ChunkSignPlan() { s3h_chunk_plan_destroy(p_); }
+  ChunkSignPlan(const ChunkSignPlan&) = delete;
+  ChunkSignPlan& operator=(const ChunkSignPlan&) = delete;
+
+  // Asynchronous: d_seeds (n x 8 words) and d_signatures (signatures() x 8 words) are device
+  // pointers, 16-byte aligned.  Call status() before using the signatures.
+  void launch(const ChunkSignContext& ctx, const void* d_base, const uint32_t* d_seeds,
+              uint32_t* d_signatures, void* stream = nullptr) {
+    sha256::batch_check(s3h_chunk_plan_launch(p_, ctx.get(), d_base, d_seeds, d_signatures, stream));
+  }
+  // The chain alone over chunk digests the caller hashed itself (device, the plan's geometry).
+  void chain(const ChunkSignContext& ctx, const uint32_t* d_chunk_digests, const uint32_t* d_seeds,
+             uint32_t* d_signatures, void* stream = nullptr) {
+    sha256::batch_check(s3h_chunk_plan_chain(p_, ctx.get(), d_chunk_digests, d_seeds, d_signatures, stream));
+  }
+  void status(void* stream = nullptr) { sha256::batch_check(s3h_chunk_plan_status(p_, stream)); }
+  uint64_t signatures() const { return signatures_; }
+  // Row of part p's first signature.
+  const std::vector<uint64_t>& signature_offsets() const { return signature_offsets_; }
+  std::string kernel() const {
+    char name[16];
+    sha256::batch_check(s3h_chunk_plan_info(p_, nullptr, nullptr, nullptr, nullptr, name, sizeof name));
+    return name;
+  }
+
+ private:
+  s3h_chunk_plan_t p_ = nullptr;
+  uint64_t signatures_ = 0;
+  std::vector<uint64_t> signature_offsets_;
+};
+
+// Host-resident parts: chunk digests on the GPUs, the chains on the CPU (s3h_chunk_sign_batch_host).
+inline std::vector<uint32_t> chunk_signatures_host(const ChunkSignContext& ctx,
+                                                   const std::vector<const uint8_t*>& parts,
+                                                   const std::vector<uint64_t>& lengths, uint64_t chunk_bytes,
+                                                   const std::vector<uint32_t>& seeds) {
+  if (parts.size() != lengths.size() || seeds.size() != 8 * parts.size())
+    throw std::invalid_argument("chunk_signatures_host: one length and one 8-word seed per part");
+  uint64_t signatures = 0;
+  sha256::batch_check(s3h_chunk_geometry(lengths.data(), lengths.size(), chunk_bytes, nullptr, nullptr,
+                                         nullptr, &signatures, nullptr));
+  std::vector<uint32_t> out(8 * signatures);
+  sha256::batch_check(s3h_chunk_sign_batch_host(ctx.get(), parts.data(), lengths.data(), parts.size(),
+                                                chunk_bytes, seeds.data(), out.data()));
+  return out;
+}
+
+// The framing line before a chunk's bytes: "<hex len>;chunk-signature=<64 hex>\r\n".
+inline std::string chunk_header_text(uint64_t chunk_len, const uint32_t* signature) {
+  char out[S3H_CHUNK_HEADER_MAX];
+  sha256::batch_check(s3h_chunk_header_text(chunk_len, signature, out, sizeof out));
+  return out;
+}
+
+}  // namespace s3h

@@ -65,12 +65,19 @@ C_ABI_SYMBOLS = (
     "s3h_sha1_batch_device", "s3h_sha1_batch_host", "s3h_sha1_file_parts",
     "s3h_sha256_sha1_batch_host", "s3h_sha256_sha1_file_parts", "s3h_cpu_sha1",
     "s3h_digest_checksum_text",
+    # SigV4 chunk-signed uploads
+    "s3h_sigv4_signing_key", "s3h_chunk_sign_ctx_create", "s3h_chunk_sign_ctx_destroy",
+    "s3h_cpu_chunk_signatures", "s3h_chunk_header_text", "s3h_chunk_geometry",
+    "s3h_chunk_plan_create", "s3h_chunk_plan_launch", "s3h_chunk_plan_chain", "s3h_chunk_plan_status",
+    "s3h_chunk_plan_info", "s3h_chunk_plan_destroy", "s3h_chunk_sign_batch_device",
+    "s3h_chunk_sign_batch_host",
 )
 CRC32C, CRC32 = 0, 1
 CRC64NVME = "crc64nvme"  # not an enum s3h_crc: the checksum has entry points of its own
 CRC_IDS = {"crc32c": CRC32C, "crc32": CRC32}
 CHECKSUM_MAX = 32
 DIGEST_CHECKSUM_MAX = 64
+CHUNK_HEADER_MAX = 104
 POLICY_IDS = {"throughput": 0, "efficiency": 1, "power": 2}
 POLICY_NAMES = {v: k for k, v in POLICY_IDS.items()}
 SOURCE_IDS = {"pinned": 0, "pageable": 1, "file": 2}
@@ -412,6 +419,34 @@ def lib() -> ctypes.CDLL:
             L.s3h_cpu_sha1.restype = None
             L.s3h_digest_checksum_text.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
                                                    ctypes.c_int, ctypes.c_char_p, ctypes.c_uint64]
+            L.s3h_sigv4_signing_key.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
+                                                ctypes.c_char_p, ctypes.c_void_p]
+            L.s3h_chunk_sign_ctx_create.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p,
+                                                    ctypes.c_char_p, ctypes.c_char_p,
+                                                    ctypes.POINTER(ctypes.c_void_p)]
+            L.s3h_chunk_sign_ctx_destroy.argtypes = [ctypes.c_void_p]
+            L.s3h_cpu_chunk_signatures.argtypes = [ctypes.c_void_p, ctypes.c_void_p, u64p,
+                                                   ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
+            L.s3h_chunk_header_text.argtypes = [ctypes.c_uint64, ctypes.c_void_p, ctypes.c_char_p,
+                                                ctypes.c_uint64]
+            L.s3h_chunk_geometry.argtypes = [u64p, ctypes.c_uint64, ctypes.c_uint64, u64p, u64p,
+                                             u64p, u64p, u64p]
+            L.s3h_chunk_plan_create.argtypes = [ctypes.c_int, u64p, u64p, ctypes.c_uint64,
+                                                ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p)]
+            L.s3h_chunk_plan_launch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+            L.s3h_chunk_plan_chain.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+            L.s3h_chunk_plan_status.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+            L.s3h_chunk_plan_info.argtypes = [ctypes.c_void_p, u64p, u64p, u64p, u64p,
+                                              ctypes.c_char_p, ctypes.c_int]
+            L.s3h_chunk_plan_destroy.argtypes = [ctypes.c_void_p]
+            L.s3h_chunk_sign_batch_device.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                      u64p, u64p, ctypes.c_uint64, ctypes.c_uint64,
+                                                      ctypes.c_void_p, ctypes.c_void_p]
+            L.s3h_chunk_sign_batch_host.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p),
+                                                    u64p, ctypes.c_uint64, ctypes.c_uint64,
+                                                    ctypes.c_void_p, ctypes.c_void_p]
             _lib = L
     return _lib
 

@@ -1,0 +1,212 @@
+// lib_chunk_sign.cpp -- CPU side of SigV4 chunk-signed uploads (aws-chunked bodies under
+// x-amz-content-sha256: STREAMING-AWS4-HMAC-SHA256-PAYLOAD): the signing key, the chunk-signing
+// context, the signature chain over ready chunk digests and the framing line of a chunk.
+//
+//   string_i = "AWS4-HMAC-SHA256-PAYLOAD\n" timestamp "\n" date/region/service/aws4_request "\n"
+//              hex(sig_{i-1}) "\n" hex(sha256("")) "\n" hex(sha256(chunk_i))
+//   sig_i    = HMAC-SHA256(signing_key, string_i),   sig_0 = the request's seed signature
+//
+// Everything before hex(sig_{i-1}) is constant (the prefix P), so the context hashes the key's
+// ipad block and P's whole blocks once; a link is the 4 or 5 blocks that remain plus one outer
+// block.  The compression is the drop-in's (SHA-NI or scalar, s3h_cpu_backend).
+#include <algorithm>
+#include <atomic>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <exception>
+#include <new>
+#include <thread>
+#include <vector>
+
+#include "../../../include/s3hash.h"
+#include "../../../include/sha256.h"
+#include "../chunk_sign.hpp"
+#include "../status.hpp"
+#include "cpu_hash.hpp"
+
+namespace {
+
+using s3h::host::fail;
+
+// sha256("")
+const uint8_t kEmptyDigest[32] = {0xe3, 0xb0, 0xc4, 0x42, 0x98, 0xfc, 0x1c, 0x14, 0x9a, 0xfb, 0xf4,
+                                  0xc8, 0x99, 0x6f, 0xb9, 0x24, 0x27, 0xae, 0x41, 0xe4, 0x64, 0x9b,
+                                  0x93, 0x4c, 0xa4, 0x95, 0x99, 0x1b, 0x78, 0x52, 0xb8, 0x55};
+
+inline void put_hex(const uint8_t *bytes, size_t n, uint8_t *out) {
+  static const char digits[] = "0123456789abcdef";
+  for (size_t i = 0; i < n; ++i) {
+    out[2 * i] = uint8_t(digits[bytes[i] >> 4]);
+    out[2 * i + 1] = uint8_t(digits[bytes[i] & 15]);
+  }
+}
+
+// One link: prev (32 raw bytes) and the chunk digest (32 raw bytes) -> sig (32 raw bytes).
+void link(const s3h_chunk_sign_ctx_s *C, const uint8_t *prev, const uint8_t *digest, uint8_t *sig) {
+  uint8_t tail[sizeof C->tail];
+  std::memcpy(tail, C->tail, 64 * C->nblk);
+  put_hex(prev, 32, tail + C->r);
+  put_hex(digest, 32, tail + C->r + 130);
+  uint32_t st[8];
+  std::memcpy(st, C->istate, sizeof st);
+  s3h::cpu::sha256_blocks(st, tail, C->nblk);
+  uint8_t outer[64] = {0};
+  for (int i = 0; i < 8; ++i) {
+    const uint32_t be = __builtin_bswap32(st[i]);
+    std::memcpy(outer + 4 * i, &be, 4);
+  }
+  outer[32] = 0x80;
+  outer[62] = 0x03;  // (64 + 32) * 8 = 768 bits
+  std::memcpy(st, C->ostate, sizeof st);
+  s3h::cpu::sha256_blocks(st, outer, 1);
+  for (int i = 0; i < 8; ++i) {
+    const uint32_t be = __builtin_bswap32(st[i]);
+    std::memcpy(sig + 4 * i, &be, 4);
+  }
+}
+
+void chain(const s3h_chunk_sign_ctx_s *C, const uint8_t *digests, uint64_t chunks, const uint8_t *seed,
+           uint8_t *sigs) {
+  const uint8_t *prev = seed;
+  for (uint64_t c = 0; c <= chunks; ++c) {
+    link(C, prev, c < chunks ? digests + 32 * c : kEmptyDigest, sigs + 32 * c);
+    prev = sigs + 32 * c;
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int s3h_sigv4_signing_key(const char *secret, const char *date, const char *region,
+                          const char *service, uint8_t key[32]) {
+  if (!secret || !date || !region || !service || !key)
+    return fail(S3H_EINVAL, "signing key: null argument");
+  std::vector<uint8_t> k0(4 + std::strlen(secret));
+  std::memcpy(k0.data(), "AWS4", 4);
+  std::memcpy(k0.data() + 4, secret, k0.size() - 4);
+  uint8_t a[32], b[32];
+  s3h_cpu_hmac256(reinterpret_cast<const uint8_t *>(date), std::strlen(date), k0.data(), k0.size(), a);
+  s3h_cpu_hmac256(reinterpret_cast<const uint8_t *>(region), std::strlen(region), a, 32, b);
+  s3h_cpu_hmac256(reinterpret_cast<const uint8_t *>(service), std::strlen(service), b, 32, a);
+  s3h_cpu_hmac256(reinterpret_cast<const uint8_t *>("aws4_request"), 12, a, 32, key);
+  return S3H_OK;
+}
+
+int s3h_chunk_sign_ctx_create(const uint8_t key[32], const char *timestamp, const char *date,
+                              const char *region, const char *service, s3h_chunk_sign_ctx_t *out) {
+  if (!out) return fail(S3H_EINVAL, "chunk sign context: null out-pointer");
+  *out = nullptr;
+  if (!key || !timestamp || !date || !region || !service)
+    return fail(S3H_EINVAL, "chunk sign context: null argument");
+  const size_t nr = std::strlen(region), ns = std::strlen(service);
+  if (std::strlen(timestamp) != 16) return fail(S3H_EINVAL, "chunk sign context: timestamp must be 16 bytes (YYYYMMDDThhmmssZ)");
+  if (std::strlen(date) != 8) return fail(S3H_EINVAL, "chunk sign context: date must be 8 bytes (YYYYMMDD)");
+  if (nr == 0 || ns == 0) return fail(S3H_EINVAL, "chunk sign context: empty region or service");
+  if (66 + nr + ns > 256)
+    return fail(S3H_EINVAL, "chunk sign context: prefix of %zu bytes (at most 256)", 66 + nr + ns);
+  auto *C = new (std::nothrow) s3h_chunk_sign_ctx_s();
+  if (!C) return fail(S3H_ENOMEM, "chunk sign context: out of memory");
+  const int plen = std::snprintf(C->prefix, sizeof C->prefix, "AWS4-HMAC-SHA256-PAYLOAD\n%s\n%s/%s/%s/aws4_request",
+                                 timestamp, date, region, service);
+  C->prefix[plen] = '\n';  // |P| <= 256: the 256th byte has no room for snprintf's NUL
+  C->prefix_len = uint32_t(plen) + 1;
+  C->r = C->prefix_len % 64;
+  C->nblk = (C->r + 203 + 63) / 64;
+
+  uint8_t pad[64];
+  for (int i = 0; i < 64; ++i) pad[i] = uint8_t((i < 32 ? key[i] : 0) ^ 0x36);
+  sha256::init_hash(C->istate);
+  s3h::cpu::sha256_blocks(C->istate, pad, 1);
+  s3h::cpu::sha256_blocks(C->istate, reinterpret_cast<const uint8_t *>(C->prefix), C->prefix_len / 64);
+  for (int i = 0; i < 64; ++i) pad[i] = uint8_t((i < 32 ? key[i] : 0) ^ 0x5c);
+  sha256::init_hash(C->ostate);
+  s3h::cpu::sha256_blocks(C->ostate, pad, 1);
+
+  // the tail: P's last r bytes, [64 hex] '\n' hex(sha256("")) '\n' [64 hex], 0x80, zeros, bit length
+  uint8_t *t = C->tail;
+  std::memcpy(t, C->prefix + C->prefix_len - C->r, C->r);
+  t[C->r + 64] = '\n';
+  put_hex(kEmptyDigest, 32, t + C->r + 65);
+  t[C->r + 129] = '\n';
+  t[C->r + 194] = 0x80;
+  const uint64_t be = __builtin_bswap64(8ull * (64 + C->prefix_len + 194));
+  std::memcpy(t + 64 * C->nblk - 8, &be, 8);
+  for (int j = 0; j < s3h::kChunkTailWords; ++j) {
+    uint32_t w;
+    std::memcpy(&w, t + 4 * j, 4);
+    C->tail_words[j] = __builtin_bswap32(w);
+  }
+  *out = C;
+  return S3H_OK;
+}
+
+int s3h_chunk_sign_ctx_destroy(s3h_chunk_sign_ctx_t ctx) {
+  delete ctx;
+  return S3H_OK;
+}
+
+int s3h_chunk_geometry(const uint64_t *lengths, uint64_t n, uint64_t chunk_bytes,
+                       uint64_t *data_chunks_per_part, uint64_t *signature_offsets,
+                       uint64_t *data_chunks, uint64_t *signatures, uint64_t *max_chunks_per_part) {
+  if (!lengths || n == 0 || n > (1ull << 31)) return fail(S3H_EINVAL, "chunk geometry: need 1 .. 2^31 parts");
+  if (chunk_bytes == 0) return fail(S3H_EINVAL, "chunk geometry: chunk_bytes must be at least 1");
+  uint64_t total = 0, longest = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    const uint64_t c = lengths[i] / chunk_bytes + (lengths[i] % chunk_bytes != 0);
+    if (c > (1ull << 31) || total + c > (1ull << 31))
+      return fail(S3H_EINVAL, "chunk geometry: more than 2^31 data chunks");
+    if (data_chunks_per_part) data_chunks_per_part[i] = c;
+    if (signature_offsets) signature_offsets[i] = total + i;
+    total += c;
+    longest = std::max(longest, c);
+  }
+  if (data_chunks) *data_chunks = total;
+  if (signatures) *signatures = total + n;
+  if (max_chunks_per_part) *max_chunks_per_part = longest;
+  return S3H_OK;
+}
+
+int s3h_cpu_chunk_signatures(s3h_chunk_sign_ctx_t ctx, const uint32_t *chunk_digests,
+                             const uint64_t *data_chunks_per_part, uint64_t n, const uint32_t *seeds,
+                             uint32_t *signatures) {
+  if (!ctx || !data_chunks_per_part || !seeds || !signatures || n == 0)
+    return fail(S3H_EINVAL, "chunk signatures: null argument or no parts");
+  std::vector<uint64_t> first(n + 1, 0);
+  for (uint64_t i = 0; i < n; ++i) first[i + 1] = first[i] + data_chunks_per_part[i];
+  if (first[n] != 0 && !chunk_digests) return fail(S3H_EINVAL, "chunk signatures: null chunk digests");
+  const uint8_t *dig = reinterpret_cast<const uint8_t *>(chunk_digests);
+  const uint8_t *seed = reinterpret_cast<const uint8_t *>(seeds);
+  uint8_t *sig = reinterpret_cast<uint8_t *>(signatures);
+  std::atomic<uint64_t> next{0};
+  auto work = [&] {
+    for (uint64_t i; (i = next.fetch_add(1)) < n;)
+      chain(ctx, dig + 32 * first[i], data_chunks_per_part[i], seed + 32 * i, sig + 32 * (first[i] + i));
+  };
+  int cpus = 1;
+  s3h_host_threads(1, &cpus);
+  // a thread per 64 links at least: starting one costs about as much as that many links
+  const uint64_t links = first[n] + n;
+  const unsigned t = unsigned(std::min<uint64_t>({uint64_t(std::max(1, cpus)), n, (links + 63) / 64}));
+  std::vector<std::thread> pool;
+  try {
+    for (unsigned k = 1; k < t; ++k) pool.emplace_back(work);
+  } catch (const std::exception &) {  // fewer threads: the ones started and this one finish
+  }
+  work();
+  for (auto &th : pool) th.join();
+  return S3H_OK;
+}
+
+int s3h_chunk_header_text(uint64_t chunk_len, const uint32_t sig[8], char *out, uint64_t out_len) {
+  if (out && out_len) out[0] = '\0';
+  if (!sig || !out || out_len < S3H_CHUNK_HEADER_MAX)
+    return fail(S3H_EINVAL, "chunk header text: need a signature and %d output bytes", S3H_CHUNK_HEADER_MAX);
+  int at = std::snprintf(out, size_t(out_len), "%llx;chunk-signature=", static_cast<unsigned long long>(chunk_len));
+  put_hex(reinterpret_cast<const uint8_t *>(sig), 32, reinterpret_cast<uint8_t *>(out) + at);
+  std::memcpy(out + at + 64, "\r\n", 3);
+  return S3H_OK;
+}
+
+}  // extern "C"

@@ -3,13 +3,15 @@
 // unit with device code), pinned host memory and device placement (pinned.cpp), and the
 // stream units' hooks.  The C-ABI itself is include/s3hash.h.
 //
-//   launch.hip    sha256_kernels.hip + sha1_kernels.hip + crc32_kernels.hip + the hipLaunchKernelGGL calls (device code)
+//   launch.hip    sha256_kernels.hip + sha1_kernels.hip + crc32_kernels.hip + chunk_sign_kernels.hip + the hipLaunchKernelGGL calls (device code)
 //   plan.cpp      plans: kernel choice, slot sorting, launches, error words; device-resident C-ABI
 //   pinned.cpp    NUMA-placed pinned host memory, device placement, s3h_host_alloc / _numa
 //   host_path.cpp host-resident pipeline (slices, groups), per-device contexts, the merge queue
 //   stream.cpp    multi-object streams (s3h_stream_*)
 //   crc.cpp       CRC-32C / CRC-32 / CRC-64/NVME plans: whole-part and ranged launches (s3h_crc_*,
 //                 s3h_crc64nvme_*), the host path's plans
+//   chunk_sign.cpp SigV4 chunk-signed uploads: chunk plans and their launches (s3h_chunk_plan_*,
+//                 s3h_chunk_sign_batch_*); context and CPU chain: cpu/lib_chunk_sign.cpp
 //   route.cpp     size-aware routing (model measurement, observed rates, routed entry points)
 //   HIP-free: status.cpp, topology.cpp, route_plan.cpp (+ copy_pool.hpp, host_queue.hpp)
 #pragma once
@@ -133,6 +135,7 @@ int launch_args(s3h_plan_s* P, const void* d_base, uint32_t* d_digests, uint32_t
 int plan_launch(s3h_plan_s* P, const void* d_base, uint32_t* d_digests, uint64_t b0, uint64_t b1,
                 uint64_t origin, hipStream_t stream, bool ranged);
 int plan_check(s3h_plan_s* P, hipStream_t s);
+const char* plan_kernel_name(const s3h_plan_s* P);  // "lane", "skew", ..., "md5", "sha1"
 
 // SHA-256 (plan S) and MD5 (plan M, same parts in the same order) from one grid:
 // kDualSplit = sha256_md5_dual_kernel (skew workgroups then MD5 workgroups, one per CU);
@@ -173,6 +176,9 @@ hipError_t launch_crc_range(const s3h::CrcRangeArgs& A, uint32_t piece_grid, hip
 // The same for CRC-64/NVME (crc64_kernels.hip): A.segs set for the whole-part launch.
 hipError_t launch_crc64(const s3h::Crc64Args& A, uint32_t seg_grid, hipStream_t s);
 hipError_t launch_crc64_range(const s3h::Crc64Args& A, uint32_t piece_grid, hipStream_t s);
+
+// The SigV4 chunk-signature chain (chunk_sign_kernels.hip): one lane per part, A.n parts.
+hipError_t launch_chunk_chain(const s3h::ChunkChainArgs& A, hipStream_t s);
 
 // ------------------------------------------------------------------ CRC plans (crc.cpp)
 // The host path's use of a plan: created once per context with the tables uploaded

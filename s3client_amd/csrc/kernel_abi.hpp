@@ -174,6 +174,32 @@ struct Crc64Args {
 constexpr int kCrc64SegThreads = 512;   // 8 waves share one copy of the tables (48.6 KiB of LDS)
 constexpr int kCrc64PartThreads = 256;  // 4 parts per workgroup
 
+// ------------------------------------------------------------- SigV4 chunk signatures (chunk_sign_kernels.hip)
+// One record per part: its data chunks' digests are digests[8 * first ...] (count of them), its
+// count + 1 signatures go to signatures[8 * sig ...].
+struct ChunkChainPart {
+  uint64_t first;
+  uint64_t sig;
+  uint32_t count;
+  uint32_t pad_;
+};
+constexpr int kChunkTailWords = 80;  // the inner tail: at most 5 blocks (r + 194 + 9 <= 266 bytes)
+// The context's midstates and tail template travel in the argument block (chunk_sign.hpp): a
+// launch uploads nothing.  `r` and `nblk` are uniform over the launch.
+struct ChunkChainArgs {
+  const uint32_t* digests;     // chunk digests, word i = bswap32(H_i)
+  const ChunkChainPart* parts;
+  const uint32_t* seeds;       // n x 8 words, the same convention
+  uint32_t* signatures;
+  uint64_t n;
+  uint32_t r;                  // |P| mod 64: the first hex field starts at tail byte r
+  uint32_t nblk;               // compressions of the inner tail (4 or 5)
+  uint32_t istate[8];
+  uint32_t ostate[8];
+  uint32_t tail[kChunkTailWords];  // big-endian words, the two 64-byte hex fields zeroed
+};
+constexpr int kChunkChainThreads = 64;  // one wave per workgroup, one lane per part
+
 // ------------------------------------------------------------- synthetic input generator
 // G(seed, p, L) of SURVEY.md 8(d): one record per part (byte offset, length, generator id).
 struct GenPart { uint64_t off, len, id; };

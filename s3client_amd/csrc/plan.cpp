@@ -202,6 +202,8 @@ double device_power_cap_w(int device) {  // cached per device (sysfs hwmon power
   return cap[device].load(std::memory_order_relaxed);
 }
 
+const char* plan_kernel_name(const s3h_plan_s* P) { return kernel_name(P); }
+
 int device_cus(int device) {  // cached: the host pipeline asks once per slice
   constexpr int kMaxDev = 64;
   static std::atomic<int> cus[kMaxDev] = {};

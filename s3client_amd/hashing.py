@@ -616,6 +616,203 @@ def digest_checksum_text(digests, algo: str = "sha1", composite: bool = False) -
 
 
 # ------------------------------------------------------------------ CRC-64/NVME checksum
+# ---------------------------------------------------------------- SigV4 chunk-signed uploads
+def sigv4_signing_key(secret: str, date: str, region: str, service: str = "s3") -> bytes:
+    """The SigV4 signing key (32 bytes) of ``secret`` for a date "YYYYMMDD", region and service
+    (s3h_sigv4_signing_key, CPU)."""
+    key = ctypes.create_string_buffer(32)
+    check(lib().s3h_sigv4_signing_key(secret.encode(), date.encode(), region.encode(),
+                                      service.encode(), key))
+    return key.raw
+
+
+class ChunkSignContext:
+    """The constant part of every chunk's string to sign of one aws-chunked request, hashed once
+    (s3h_chunk_sign_ctx_create): signing key, timestamp "YYYYMMDDThhmmssZ", date, region,
+    service.  Immutable; CPU."""
+
+    def __init__(self, key: bytes, timestamp: str, date: str, region: str, service: str = "s3"):
+        if len(key) != 32:
+            raise ValueError("the signing key is 32 bytes")
+        h = ctypes.c_void_p()
+        check(lib().s3h_chunk_sign_ctx_create(bytes(key), timestamp.encode(), date.encode(),
+                                              region.encode(), service.encode(), ctypes.byref(h)))
+        self._h = h
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            lib().s3h_chunk_sign_ctx_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def chunk_geometry(lengths, chunk_bytes: int) -> dict:
+    """Chunk geometry of parts of ``lengths`` cut at ``chunk_bytes`` (s3h_chunk_geometry, no
+    GPU): per part its data chunks and the index of its first signature, and the totals."""
+    lens = _u64(lengths)
+    n = int(lens.size)
+    counts, sig = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
+    chunks, sigs, longest = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+    check(lib().s3h_chunk_geometry(_p64(lens), n, int(chunk_bytes), _p64(counts), _p64(sig),
+                                   ctypes.byref(chunks), ctypes.byref(sigs), ctypes.byref(longest)))
+    return {"n": n, "data_chunks_per_part": counts, "signature_offsets": sig,
+            "data_chunks": chunks.value, "signatures": sigs.value,
+            "max_chunks_per_part": longest.value}
+
+
+def _words(a, rows: int | None, what: str) -> np.ndarray:
+    """(rows, 8) uint32 view of signatures / digests given as words or raw bytes."""
+    if isinstance(a, (bytes, bytearray, memoryview)):
+        a = np.frombuffer(a, dtype=np.uint8)
+    a = np.ascontiguousarray(a).reshape(-1).view(np.uint8).view(np.uint32).reshape(-1, 8)
+    if rows is not None and a.shape[0] != rows:
+        raise ValueError(f"{what}: {a.shape[0]} rows of 8 words, expected {rows}")
+    return a
+
+
+def cpu_chunk_signatures(ctx: ChunkSignContext, chunk_digests, data_chunks_per_part,
+                         seeds) -> np.ndarray:
+    """The signature chains on the CPU over ready chunk digests (s3h_cpu_chunk_signatures):
+    ``chunk_digests`` (data chunks, 8) words part-major, ``data_chunks_per_part`` n counts,
+    ``seeds`` (n, 8).  Returns (data chunks + n, 8) uint32, part-major: each part's data-chunk
+    signatures, then the signature of its final 0-byte chunk."""
+    counts = _u64(data_chunks_per_part)
+    n, total = int(counts.size), int(counts.sum())
+    dig = _words(chunk_digests, total, "chunk digests") if total else None
+    sd = _words(seeds, n, "seeds")
+    out = np.zeros((total + n, 8), dtype=np.uint32)
+    check(lib().s3h_cpu_chunk_signatures(ctx._h, dig.ctypes.data if total else None, _p64(counts),
+                                         n, sd.ctypes.data, out.ctypes.data))
+    return out
+
+
+def chunk_header_text(chunk_len: int, signature) -> str:
+    """The framing line before a chunk: "<hex len>;chunk-signature=<64 hex>\r\n"."""
+    sig = _words(signature, 1, "signature")
+    buf = ctypes.create_string_buffer(_native.CHUNK_HEADER_MAX)
+    check(lib().s3h_chunk_header_text(int(chunk_len), sig.ctypes.data, buf, len(buf)))
+    return buf.value.decode()
+
+
+class ChunkSignPlan:
+    """Device-resident parts cut into chunks of ``chunk_bytes``: a SHA-256 plan over the chunks
+    plus each part's chain record (s3h_chunk_plan_create).  ``signature_offsets[p]`` is the row
+    of part p's first signature; part p has ``data_chunks_per_part[p] + 1`` of them."""
+
+    def __init__(self, offsets: Sequence[int], lengths: Sequence[int], chunk_bytes: int,
+                 device: int = 0):
+        self.offsets, self.lengths = _u64(offsets), _u64(lengths)
+        if self.offsets.shape != self.lengths.shape or self.offsets.ndim != 1:
+            raise ValueError("offsets and lengths must be 1-D and of equal length")
+        self.n = int(self.lengths.size)
+        self.chunk_bytes = int(chunk_bytes)
+        self.device = device
+        g = chunk_geometry(self.lengths, self.chunk_bytes)
+        self.data_chunks_per_part = g["data_chunks_per_part"]
+        self.signature_offsets = g["signature_offsets"]
+        self.signatures = g["signatures"]
+        h = ctypes.c_void_p()
+        check(lib().s3h_chunk_plan_create(device, _p64(self.offsets), _p64(self.lengths), self.n,
+                                          self.chunk_bytes, ctypes.byref(h)))
+        self._h = h
+
+    def info(self) -> dict:
+        n, c, s, m = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        name = ctypes.create_string_buffer(16)
+        check(lib().s3h_chunk_plan_info(self._h, ctypes.byref(n), ctypes.byref(c), ctypes.byref(s),
+                                        ctypes.byref(m), name, len(name)))
+        return {"n": n.value, "data_chunks": c.value, "signatures": s.value,
+                "max_chunks_per_part": m.value, "kernel": name.value.decode()}
+
+    def launch(self, data, ctx: ChunkSignContext, seeds, out, stream=None) -> None:
+        """Hash every chunk of ``data`` and chain the signatures into ``out`` (signatures x 8
+        words) from ``seeds`` (n x 8 words).  Device tensors, or raw device pointers (ints)."""
+        ptrs = []
+        for t, need in ((data, int((self.offsets + self.lengths).max()) if self.n else 0),
+                        (seeds, 32 * self.n), (out, 32 * self.signatures)):
+            if isinstance(t, int):
+                ptrs.append(t)
+                continue
+            if not t.is_cuda:
+                raise ValueError("data, seeds and out must be device tensors")
+            if t.numel() * t.element_size() < need:
+                raise ValueError(f"buffer of {t.numel() * t.element_size()} B, need {need} B")
+            ptrs.append(t.data_ptr())
+        check(lib().s3h_chunk_plan_launch(self._h, ctx._h, ctypes.c_void_p(ptrs[0]),
+                                          ctypes.c_void_p(ptrs[1]), ctypes.c_void_p(ptrs[2]),
+                                          ctypes.c_void_p(_stream_handle(stream))))
+
+    def chain(self, ctx: ChunkSignContext, chunk_digests, seeds, out, stream=None) -> None:
+        """The chain kernel alone over ``chunk_digests`` (device tensor, data chunks x 8 words in
+        this plan's geometry) that the caller hashed itself (s3h_chunk_plan_chain)."""
+        chunks = int(self.data_chunks_per_part.sum())
+        for t, need in ((chunk_digests, 32 * chunks), (seeds, 32 * self.n), (out, 32 * self.signatures)):
+            if not t.is_cuda or t.numel() * t.element_size() < need:
+                raise ValueError(f"need a device tensor of at least {need} B")
+        check(lib().s3h_chunk_plan_chain(self._h, ctx._h, ctypes.c_void_p(chunk_digests.data_ptr()),
+                                         ctypes.c_void_p(seeds.data_ptr()), ctypes.c_void_p(out.data_ptr()),
+                                         ctypes.c_void_p(_stream_handle(stream))))
+
+    def status(self, stream=None) -> None:
+        """Wait for ``stream``; raise if a chunk-hash launch since the last check reported a
+        fault (s3h_chunk_plan_status)."""
+        check(lib().s3h_chunk_plan_status(self._h, ctypes.c_void_p(_stream_handle(stream))))
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            lib().s3h_chunk_plan_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def chunk_sign_batch_device(data, offsets, lengths, chunk_bytes: int, ctx: ChunkSignContext,
+                            seeds) -> np.ndarray:
+    """One-shot: plan, launch, copy back (s3h_chunk_sign_batch_device).  ``data`` is a device
+    tensor, ``seeds`` host (n, 8) words; returns host (signatures, 8) uint32."""
+    offs, lens = _u64(offsets), _u64(lengths)
+    n = int(lens.size)
+    sd = _words(seeds, n, "seeds")
+    out = np.zeros((chunk_geometry(lens, chunk_bytes)["signatures"], 8), dtype=np.uint32)
+    check(lib().s3h_chunk_sign_batch_device(data.device.index or 0, ctx._h,
+                                            ctypes.c_void_p(data.data_ptr()), _p64(offs), _p64(lens),
+                                            n, int(chunk_bytes), sd.ctypes.data, out.ctypes.data))
+    return out
+
+
+def chunk_sign_host(parts: Sequence, chunk_bytes: int, ctx: ChunkSignContext, seeds) -> np.ndarray:
+    """Host-resident parts: chunk digests through the host pipeline, the chain on the CPU
+    (s3h_chunk_sign_batch_host).  Returns (signatures, 8) uint32, part-major."""
+    arrs, ptrs, lens = _host_parts(parts)
+    n = len(arrs)
+    sd = _words(seeds, n, "seeds")
+    out = np.zeros((chunk_geometry(lens, chunk_bytes)["signatures"], 8), dtype=np.uint32)
+    check(lib().s3h_chunk_sign_batch_host(ctx._h, ptrs, _p64(lens), n, int(chunk_bytes),
+                                          sd.ctypes.data, out.ctypes.data))
+    return out
+
+
 class Crc64Plan(CrcPlan):
     """CrcPlan for CRC-64/NVME (x-amz-checksum-crc64nvme; s3h_crc64nvme_plan_create): the same
     ``launch`` / ``launch_range`` / ``info``, with ``crcs`` holding n 64-bit words."""

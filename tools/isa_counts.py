@@ -63,6 +63,8 @@ ALL_KERNELS = {
     "crc64_range_parts": "_ZN3s3h24crc64_range_parts_kernelENS_9Crc64ArgsE",
     # SHA-1 (sha1_kernels.hip)
     "sha1-pc": KERNELS["sha1-pc"][0], "sha1-pc1": KERNELS["sha1-pc1"][0],
+    # SigV4 chunk-signature chain (chunk_sign_kernels.hip): code hash only
+    "chunk-chain": "_ZN3s3h24sigv4_chunk_chain_kernelENS_14ChunkChainArgsE",
 }
 FLAG_KERNELS = ("skew_nc2", "skews", "dual_group", "dual_group_skew", "dual_group_mixed")
 ERR_STORE = re.compile(r"^\t(global|flat|buffer)_atomic_or\b")
