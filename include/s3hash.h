@@ -23,6 +23,9 @@
  *       _host, s3h_cpu_chunk_signatures, s3h_chunk_header_text  -- aws-chunked bodies signed per
  *       chunk (STREAMING-AWS4-HMAC-SHA256-PAYLOAD), which the reference's signer does not
  *       produce (lib/src/aws_sign.cpp signs whole payloads): chunk hashes and the HMAC chain.
+ *   s3h_chunk_plan_create_trailer / _launch_trailer / _trailer, s3h_chunk_sign_trailer_batch_*,
+ *       s3h_cpu_trailer_signatures, s3h_chunk_trailer_text  -- the same bodies closed by a trailing
+ *       checksum header and its signature (STREAMING-AWS4-HMAC-SHA256-PAYLOAD-TRAILER).
  *
  * Digest layout (every entry point): 8 uint32 words per part with word i = bswap32(H_i),
  * exactly lib/hash's `to_little` output (sha256.h:103-106); on little-endian hosts the 32
@@ -48,7 +51,10 @@ extern "C" {
  * s3h_sha1_batch_device, s3h_sha1_batch_host, s3h_sha1_file_parts, s3h_sha256_sha1_batch_host,
  * s3h_sha256_sha1_file_parts, s3h_cpu_sha1, s3h_digest_checksum_text), then SigV4 chunk-signed
  * uploads (s3h_sigv4_signing_key, s3h_chunk_sign_ctx_*, s3h_cpu_chunk_signatures,
- * s3h_chunk_header_text, s3h_chunk_geometry, s3h_chunk_plan_*, s3h_chunk_sign_batch_device / _host). */
+ * s3h_chunk_header_text, s3h_chunk_geometry, s3h_chunk_plan_*, s3h_chunk_sign_batch_device / _host),
+ * then their trailer signatures (s3h_cpu_trailer_signatures, s3h_trailer_line_text,
+ * s3h_chunk_trailer_text, s3h_chunk_plan_create_trailer, s3h_chunk_plan_launch_trailer,
+ * s3h_chunk_plan_trailer, s3h_chunk_plan_trailer_info, s3h_chunk_sign_trailer_batch_device / _host). */
 #define S3H_API_VERSION 2
 
 enum s3h_status {
@@ -729,7 +735,8 @@ int s3h_digest_checksum_text(int algo, const uint32_t *digests, uint64_t n, int 
  * host-resident entry point runs it on the CPU, where the digests land anyway.  A device caller
  * with a few long parts is better off hashing the chunks with an ordinary SHA-256 plan and
  * calling s3h_cpu_chunk_signatures: one GPU lane walks a chain ~100x slower than one CPU core.
- * The trailer variant (...-PAYLOAD-TRAILER) is not covered.  Added within API version 2. */
+ * The trailer variant (...-PAYLOAD-TRAILER): the section after this one.  Added within API
+ * version 2. */
 typedef struct s3h_chunk_sign_ctx_s *s3h_chunk_sign_ctx_t;
 typedef struct s3h_chunk_plan_s *s3h_chunk_plan_t;
 /* signing_key = HMAC(HMAC(HMAC(HMAC("AWS4" + secret, date), region), service), "aws4_request")
@@ -806,6 +813,93 @@ int s3h_chunk_sign_batch_device(int device, s3h_chunk_sign_ctx_t ctx, const void
 int s3h_chunk_sign_batch_host(s3h_chunk_sign_ctx_t ctx, const uint8_t *const *parts,
                               const uint64_t *lengths, uint64_t n, uint64_t chunk_bytes,
                               const uint32_t *seeds, uint32_t *signatures);
+
+/* ---------------------------------------------------------------- SigV4 trailer signatures
+ * x-amz-content-sha256: STREAMING-AWS4-HMAC-SHA256-PAYLOAD-TRAILER, the form current SDKs send:
+ * the chunk-signed body above (the chunk strings keep AWS4-HMAC-SHA256-PAYLOAD; only the seed,
+ * signed over other headers, differs), closed by one trailing checksum header and a signature
+ * over it.  With sig_last the signature of the part's final 0-byte chunk:
+ *   line        = name ":" base64(value) "\n"         e.g. "x-amz-checksum-crc32c:sOO8/Q==\n"
+ *   trailer_sig = HMAC-SHA256(signing_key, "AWS4-HMAC-SHA256-TRAILER\n" timestamp "\n"
+ *                   date "/" region "/" service "/aws4_request\n" hex(sig_last) "\n"
+ *                   hex(sha256(line)))
+ * `value` is the checksum's big-endian bytes: 4 (CRC-32C, CRC-32), 8 (CRC-64/NVME), 20 (SHA-1)
+ * or 32 (SHA-256); the hashed line ends in "\n" (not "\r\n", which is only the framing).  Value
+ * arrays have the layouts the library returns elsewhere: one uint32_t per part for the 32-bit
+ * CRCs, one uint64_t for CRC-64/NVME, 5 or 8 words per part for the digests; trailer signatures
+ * are 8 words per part like every signature.  A CRC plan cuts a part into segments as the chunk
+ * plan cuts it into chunks, so neither half is a serial chain per part and one large part still
+ * fills the GPU.  The digest checksums are accepted by the CPU functions and the host-resident
+ * entry point only: a part's SHA-1 or SHA-256 is a whole-part chain, which is what chunk signing
+ * exists to avoid, so the device entry points return S3H_EINVAL for them.
+ * The framing s3h_chunk_trailer_text writes follows the AWS documentation; it has not been
+ * pinned against a real server (the tests' mock endpoint does not decode aws-chunked bodies).
+ * Added within API version 2. */
+enum s3h_trailer_checksum {
+  S3H_TRAILER_CRC32C = 0,
+  S3H_TRAILER_CRC32 = 1,
+  S3H_TRAILER_CRC64NVME = 2,
+  S3H_TRAILER_SHA1 = 3,
+  S3H_TRAILER_SHA256 = 4
+};
+/* The trailer link on the CPU, from the context's midstates: values (n entries in the kind's
+ * layout), last_signatures (n x 8 words: each part's last chunk signature, gathered) ->
+ * trailer_signatures (n x 8 words).  Every kind.  Parts are spread over the host threads. */
+int s3h_cpu_trailer_signatures(s3h_chunk_sign_ctx_t ctx, int checksum, const void *values,
+                               const uint32_t *last_signatures, uint64_t n,
+                               uint32_t *trailer_signatures);
+/* "name:base64" of one value (no line end), NUL-terminated, out_len >= S3H_TRAILER_LINE_MAX. */
+#define S3H_TRAILER_LINE_MAX 80
+int s3h_trailer_line_text(int checksum, const void *value, char *out, uint64_t out_len);
+/* What an uploader writes after the "0;chunk-signature=...\r\n" line of s3h_chunk_header_text:
+ *   name:base64\r\n
+ *   x-amz-trailer-signature:<64 hex>\r\n
+ *   \r\n
+ * NUL-terminated, out_len >= S3H_CHUNK_TRAILER_MAX. */
+#define S3H_CHUNK_TRAILER_MAX 192
+int s3h_chunk_trailer_text(int checksum, const void *value, const uint32_t trailer_sig[8],
+                           char *out, uint64_t out_len);
+/* s3h_chunk_plan_create plus a CRC plan over the whole parts (s3h_crc_plan_* or
+ * s3h_crc64nvme_plan_*, owned by the chunk plan).  checksum: S3H_TRAILER_CRC32C, _CRC32 or
+ * _CRC64NVME (the digests: S3H_EINVAL, above).  The plan serves every s3h_chunk_plan_* call. */
+int s3h_chunk_plan_create_trailer(int device, int checksum, const uint64_t *offsets,
+                                  const uint64_t *lengths, uint64_t n, uint64_t chunk_bytes,
+                                  s3h_chunk_plan_t *out);
+/* Asynchronous on `stream`, in stream order with no host work between: the chunk hashes, the
+ * chain, the CRC launch, the trailer kernel.  d_seeds and d_signatures as for
+ * s3h_chunk_plan_launch; d_checksums receives n values (4-byte aligned words, or 8-byte aligned
+ * 64-bit words for CRC-64/NVME: the uploader needs them for the trailer text; an empty part
+ * gives 0); d_trailer_signatures n x 8 words, 16-byte aligned.  Nothing behind the last entry of
+ * an output is written.  S3H_EINVAL for a plan made by s3h_chunk_plan_create. */
+int s3h_chunk_plan_launch_trailer(s3h_chunk_plan_t plan, s3h_chunk_sign_ctx_t ctx,
+                                  const void *d_base, const uint32_t *d_seeds,
+                                  uint32_t *d_signatures, void *d_checksums,
+                                  uint32_t *d_trailer_signatures, void *stream);
+/* The trailer kernel alone, over chunk signatures (the plan's geometry) and checksum values
+ * already on the device: the counterpart of s3h_chunk_plan_chain.  Asynchronous on `stream`. */
+int s3h_chunk_plan_trailer(s3h_chunk_plan_t plan, s3h_chunk_sign_ctx_t ctx,
+                           const uint32_t *d_signatures, const void *d_checksums,
+                           uint32_t *d_trailer_signatures, void *stream);
+/* The plan's checksum kind (enum s3h_trailer_checksum), or -1 for a plan without a trailer. */
+int s3h_chunk_plan_trailer_info(s3h_chunk_plan_t plan, int *checksum);
+/* One-shot, blocking: plan + launch + status + copy back.  d_base is a device pointer; seeds_host,
+ * signatures_host (as s3h_chunk_sign_batch_device), checksums_host (n values) and
+ * trailer_signatures_host (n x 8 words) are host memory. */
+int s3h_chunk_sign_trailer_batch_device(int device, s3h_chunk_sign_ctx_t ctx, int checksum,
+                                        const void *d_base, const uint64_t *offsets,
+                                        const uint64_t *lengths, uint64_t n, uint64_t chunk_bytes,
+                                        const uint32_t *seeds_host, uint32_t *signatures_host,
+                                        void *checksums_host, uint32_t *trailer_signatures_host);
+/* Host-resident parts.  CRC kinds: the chunks go once through s3h_sha256_crc_batch_host /
+ * s3h_sha256_crc64nvme_batch_host as its parts, each part's chunk CRCs are folded
+ * (s3h_crc_object / s3h_crc64nvme_object: no second read of the data), then the chain and the
+ * trailer link run on the CPU.  Digest kinds: the chunks through s3h_sha256_batch_host and the
+ * whole parts through s3h_sha1_batch_host / s3h_sha256_batch_host.  Blocking. */
+int s3h_chunk_sign_trailer_batch_host(s3h_chunk_sign_ctx_t ctx, int checksum,
+                                      const uint8_t *const *parts, const uint64_t *lengths,
+                                      uint64_t n, uint64_t chunk_bytes, const uint32_t *seeds,
+                                      uint32_t *signatures, void *checksums,
+                                      uint32_t *trailer_signatures);
 
 /* ---------------------------------------------------------------- synthetic inputs
  * Fill part i (at d_base + offsets[i], 8-B aligned, lengths[i] bytes) with generator

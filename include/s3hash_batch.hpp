@@ -663,4 +663,117 @@ inline std::string chunk_header_text(uint64_t chunk_len, const uint32_t* signatu
   return out;
 }
 
+// ---- trailer signatures (STREAMING-AWS4-HMAC-SHA256-PAYLOAD-TRAILER): the same bodies closed by
+// one trailing checksum header and a signature over it.  `checksum` is an s3h_trailer_checksum;
+// values are uint32_t (CRC-32C, CRC-32) or uint64_t (CRC-64/NVME) per part, or 5 / 8 words per
+// part for the SHA-1 / SHA-256 digests (CPU and host-resident forms only).
+
+// The trailer link on the CPU (s3h_cpu_trailer_signatures): one value and one last chunk
+// signature (8 words) per part -> 8 words per part.
+template <class Value>
+inline std::vector<uint32_t> trailer_signatures(const ChunkSignContext& ctx, int checksum,
+                                                const std::vector<Value>& values,
+                                                const std::vector<uint32_t>& last_signatures) {
+  static_assert(sizeof(Value) == 4 || sizeof(Value) == 8, "uint32_t values or words, or uint64_t values");
+  const uint64_t n = last_signatures.size() / 8;
+  const uint64_t per = checksum == S3H_TRAILER_SHA1 ? 5 : checksum == S3H_TRAILER_SHA256 ? 8 : 1;
+  const bool wide = checksum == S3H_TRAILER_CRC64NVME;
+  if (last_signatures.size() != 8 * n || values.size() != per * n || (sizeof(Value) == 8) != wide)
+    throw std::invalid_argument("trailer_signatures: one value of the checksum's type and 8 signature words per part");
+  std::vector<uint32_t> out(8 * n);
+  sha256::batch_check(s3h_cpu_trailer_signatures(ctx.get(), checksum, values.data(), last_signatures.data(), n,
+                                                 out.data()));
+  return out;
+}
+
+// "name:base64" of one value (s3h_trailer_line_text).
+inline std::string trailer_line_text(int checksum, const void* value) {
+  char out[S3H_TRAILER_LINE_MAX];
+  sha256::batch_check(s3h_trailer_line_text(checksum, value, out, sizeof out));
+  return out;
+}
+
+// What follows the "0;chunk-signature=...\r\n" line: the trailing header, the
+// x-amz-trailer-signature line and the empty line (s3h_chunk_trailer_text).
+inline std::string chunk_trailer_text(int checksum, const void* value, const uint32_t* trailer_signature) {
+  char out[S3H_CHUNK_TRAILER_MAX];
+  sha256::batch_check(s3h_chunk_trailer_text(checksum, value, trailer_signature, out, sizeof out));
+  return out;
+}
+
+// A ChunkSignPlan that also owns a CRC plan over the whole parts (s3h_chunk_plan_create_trailer):
+// checksum S3H_TRAILER_CRC32C, _CRC32 or _CRC64NVME.
+class ChunkTrailerPlan {
+ public:
+  ChunkTrailerPlan(int device, int checksum, const std::vector<uint64_t>& offsets,
+                   const std::vector<uint64_t>& lengths, uint64_t chunk_bytes)
+      : checksum_(checksum) {
+    if (offsets.size() != lengths.size()) throw std::invalid_argument("offsets/lengths size mismatch");
+    sha256::batch_check(s3h_chunk_plan_create_trailer(device, checksum, offsets.data(), lengths.data(),
+                                                      offsets.size(), chunk_bytes, &p_));
+    signature_offsets_.resize(lengths.size());
+    sha256::batch_check(s3h_chunk_geometry(lengths.data(), lengths.size(), chunk_bytes, nullptr,
+                                           signature_offsets_.data(), nullptr, &signatures_, nullptr));
+  }
+  ~ChunkTrailerPlan() { s3h_chunk_plan_destroy(p_); }
+  ChunkTrailerPlan(const ChunkTrailerPlan&) = delete;
+  ChunkTrailerPlan& operator=(const ChunkTrailerPlan&) = delete;
+
+  // Asynchronous: chunk hashes, chain, CRCs, trailer kernel on `stream`.  Device pointers:
+  // d_seeds n x 8 words, d_signatures signatures() x 8 words, d_checksums n values,
+  // d_trailer_signatures n x 8 words.  Call status() before using the outputs.
+  void launch(const ChunkSignContext& ctx, const void* d_base, const uint32_t* d_seeds, uint32_t* d_signatures,
+              void* d_checksums, uint32_t* d_trailer_signatures, void* stream = nullptr) {
+    sha256::batch_check(s3h_chunk_plan_launch_trailer(p_, ctx.get(), d_base, d_seeds, d_signatures, d_checksums,
+                                                      d_trailer_signatures, stream));
+  }
+  // The trailer kernel alone over chunk signatures and checksum values already on the device.
+  void trailer(const ChunkSignContext& ctx, const uint32_t* d_signatures, const void* d_checksums,
+               uint32_t* d_trailer_signatures, void* stream = nullptr) {
+    sha256::batch_check(s3h_chunk_plan_trailer(p_, ctx.get(), d_signatures, d_checksums, d_trailer_signatures,
+                                               stream));
+  }
+  void status(void* stream = nullptr) { sha256::batch_check(s3h_chunk_plan_status(p_, stream)); }
+  int checksum() const { return checksum_; }
+  uint64_t signatures() const { return signatures_; }
+  const std::vector<uint64_t>& signature_offsets() const { return signature_offsets_; }
+  s3h_chunk_plan_t get() const { return p_; }
+
+ private:
+  s3h_chunk_plan_t p_ = nullptr;
+  int checksum_;
+  uint64_t signatures_ = 0;
+  std::vector<uint64_t> signature_offsets_;
+};
+
+// Host-resident parts (s3h_chunk_sign_trailer_batch_host): the chunk signatures, the checksums
+// (as bytes in the kind's layout: 4, 8, 20 or 32 per part) and the trailer signatures.
+struct ChunkTrailerResult {
+  std::vector<uint32_t> signatures;
+  std::vector<uint8_t> checksums;
+  std::vector<uint32_t> trailer_signatures;
+};
+inline ChunkTrailerResult chunk_trailer_signatures_host(const ChunkSignContext& ctx, int checksum,
+                                                        const std::vector<const uint8_t*>& parts,
+                                                        const std::vector<uint64_t>& lengths,
+                                                        uint64_t chunk_bytes, const std::vector<uint32_t>& seeds) {
+  if (parts.size() != lengths.size() || seeds.size() != 8 * parts.size())
+    throw std::invalid_argument("chunk_trailer_signatures_host: one length and one 8-word seed per part");
+  uint64_t signatures = 0;
+  sha256::batch_check(s3h_chunk_geometry(lengths.data(), lengths.size(), chunk_bytes, nullptr, nullptr,
+                                         nullptr, &signatures, nullptr));
+  ChunkTrailerResult r;
+  r.signatures.resize(8 * signatures);
+  r.checksums.resize(32 * parts.size());  // room for the widest kind
+  r.trailer_signatures.resize(8 * parts.size());
+  sha256::batch_check(s3h_chunk_sign_trailer_batch_host(ctx.get(), checksum, parts.data(), lengths.data(),
+                                                        parts.size(), chunk_bytes, seeds.data(),
+                                                        r.signatures.data(), r.checksums.data(),
+                                                        r.trailer_signatures.data()));
+  const uint64_t per = checksum == S3H_TRAILER_CRC64NVME ? 8 : checksum == S3H_TRAILER_SHA1 ? 20
+                       : checksum == S3H_TRAILER_SHA256 ? 32 : 4;
+  r.checksums.resize(per * parts.size());
+  return r;
+}
+
 }  // namespace s3h

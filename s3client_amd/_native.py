@@ -71,7 +71,17 @@ C_ABI_SYMBOLS = (
     "s3h_chunk_plan_create", "s3h_chunk_plan_launch", "s3h_chunk_plan_chain", "s3h_chunk_plan_status",
     "s3h_chunk_plan_info", "s3h_chunk_plan_destroy", "s3h_chunk_sign_batch_device",
     "s3h_chunk_sign_batch_host",
+    # SigV4 trailer signatures (chunk-signed uploads with a trailing checksum header)
+    "s3h_cpu_trailer_signatures", "s3h_trailer_line_text", "s3h_chunk_trailer_text",
+    "s3h_chunk_plan_create_trailer", "s3h_chunk_plan_launch_trailer", "s3h_chunk_plan_trailer",
+    "s3h_chunk_plan_trailer_info", "s3h_chunk_sign_trailer_batch_device",
+    "s3h_chunk_sign_trailer_batch_host",
 )
+# enum s3h_trailer_checksum, and the numpy layout of one value of each kind
+TRAILER_IDS = {"crc32c": 0, "crc32": 1, "crc64nvme": 2, "sha1": 3, "sha256": 4}
+TRAILER_VALUE = {0: ("<u4", 1), 1: ("<u4", 1), 2: ("<u8", 1), 3: ("<u4", 5), 4: ("<u4", 8)}
+TRAILER_LINE_MAX = 80
+CHUNK_TRAILER_MAX = 192
 CRC32C, CRC32 = 0, 1
 CRC64NVME = "crc64nvme"  # not an enum s3h_crc: the checksum has entry points of its own
 CRC_IDS = {"crc32c": CRC32C, "crc32": CRC32}
@@ -447,6 +457,28 @@ def lib() -> ctypes.CDLL:
             L.s3h_chunk_sign_batch_host.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p),
                                                     u64p, ctypes.c_uint64, ctypes.c_uint64,
                                                     ctypes.c_void_p, ctypes.c_void_p]
+            L.s3h_cpu_trailer_signatures.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                                     ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
+            L.s3h_trailer_line_text.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_char_p,
+                                                ctypes.c_uint64]
+            L.s3h_chunk_trailer_text.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                 ctypes.c_char_p, ctypes.c_uint64]
+            L.s3h_chunk_plan_create_trailer.argtypes = [ctypes.c_int, ctypes.c_int, u64p, u64p,
+                                                        ctypes.c_uint64, ctypes.c_uint64,
+                                                        ctypes.POINTER(ctypes.c_void_p)]
+            L.s3h_chunk_plan_launch_trailer.argtypes = [ctypes.c_void_p] * 8
+            L.s3h_chunk_plan_trailer.argtypes = [ctypes.c_void_p] * 6
+            L.s3h_chunk_plan_trailer_info.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
+            L.s3h_chunk_sign_trailer_batch_device.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+                                                              ctypes.c_void_p, u64p, u64p,
+                                                              ctypes.c_uint64, ctypes.c_uint64,
+                                                              ctypes.c_void_p, ctypes.c_void_p,
+                                                              ctypes.c_void_p, ctypes.c_void_p]
+            L.s3h_chunk_sign_trailer_batch_host.argtypes = [ctypes.c_void_p, ctypes.c_int,
+                                                            ctypes.POINTER(ctypes.c_void_p), u64p,
+                                                            ctypes.c_uint64, ctypes.c_uint64,
+                                                            ctypes.c_void_p, ctypes.c_void_p,
+                                                            ctypes.c_void_p, ctypes.c_void_p]
             _lib = L
     return _lib
 

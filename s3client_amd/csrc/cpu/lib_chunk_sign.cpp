@@ -9,6 +9,11 @@
 // Everything before hex(sig_{i-1}) is constant (the prefix P), so the context hashes the key's
 // ipad block and P's whole blocks once; a link is the 4 or 5 blocks that remain plus one outer
 // block.  The compression is the drop-in's (SHA-NI or scalar, s3h_cpu_backend).
+//
+// The trailer variant (...-PAYLOAD-TRAILER) closes a part with a trailing checksum header and
+//   trailer_sig = HMAC-SHA256(signing_key, P' hex(sig_last) "\n" hex(sha256(name ":" base64 "\n")))
+// P' being P under the name AWS4-HMAC-SHA256-TRAILER: one more link, 3 or 4 inner blocks, from a
+// midstate and a tail template of its own (chunk_sign.hpp).
 #include <algorithm>
 #include <atomic>
 #include <cstdint>
@@ -42,15 +47,12 @@ inline void put_hex(const uint8_t *bytes, size_t n, uint8_t *out) {
   }
 }
 
-// One link: prev (32 raw bytes) and the chunk digest (32 raw bytes) -> sig (32 raw bytes).
-void link(const s3h_chunk_sign_ctx_s *C, const uint8_t *prev, const uint8_t *digest, uint8_t *sig) {
-  uint8_t tail[sizeof C->tail];
-  std::memcpy(tail, C->tail, 64 * C->nblk);
-  put_hex(prev, 32, tail + C->r);
-  put_hex(digest, 32, tail + C->r + 130);
+// HMAC from the midstates: `nblk` blocks of `tail` from the inner one, then the outer block.
+void finish(const uint32_t istate[8], const uint32_t ostate[8], const uint8_t *tail, uint32_t nblk,
+            uint8_t *sig) {
   uint32_t st[8];
-  std::memcpy(st, C->istate, sizeof st);
-  s3h::cpu::sha256_blocks(st, tail, C->nblk);
+  std::memcpy(st, istate, sizeof st);
+  s3h::cpu::sha256_blocks(st, tail, nblk);
   uint8_t outer[64] = {0};
   for (int i = 0; i < 8; ++i) {
     const uint32_t be = __builtin_bswap32(st[i]);
@@ -58,12 +60,86 @@ void link(const s3h_chunk_sign_ctx_s *C, const uint8_t *prev, const uint8_t *dig
   }
   outer[32] = 0x80;
   outer[62] = 0x03;  // (64 + 32) * 8 = 768 bits
-  std::memcpy(st, C->ostate, sizeof st);
+  std::memcpy(st, ostate, sizeof st);
   s3h::cpu::sha256_blocks(st, outer, 1);
   for (int i = 0; i < 8; ++i) {
     const uint32_t be = __builtin_bswap32(st[i]);
     std::memcpy(sig + 4 * i, &be, 4);
   }
+}
+
+// One link: prev (32 raw bytes) and the chunk digest (32 raw bytes) -> sig (32 raw bytes).
+void link(const s3h_chunk_sign_ctx_s *C, const uint8_t *prev, const uint8_t *digest, uint8_t *sig) {
+  uint8_t tail[sizeof C->tail];
+  std::memcpy(tail, C->tail, 64 * C->nblk);
+  put_hex(prev, 32, tail + C->r);
+  put_hex(digest, 32, tail + C->r + 130);
+  finish(C->istate, C->ostate, tail, C->nblk, sig);
+}
+
+const s3h::TrailerKind kTrailerKinds[] = {{"x-amz-checksum-crc32c", 4, 8},
+                                          {"x-amz-checksum-crc32", 4, 8},
+                                          {"x-amz-checksum-crc64nvme", 8, 12},
+                                          {"x-amz-checksum-sha1", 20, 28},
+                                          {"x-amz-checksum-sha256", 32, 44}};
+constexpr size_t kTrailerLineMax = 24 + 1 + 44 + 1;  // the longest name, ':', the longest text, '\n'
+
+size_t base64(const uint8_t *in, size_t n, char *out) {
+  static const char *const a = "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789+/";
+  size_t o = 0;
+  for (size_t i = 0; i < n; i += 3) {
+    const size_t left = n - i;
+    const uint32_t v = uint32_t(in[i]) << 16 | (left > 1 ? uint32_t(in[i + 1]) << 8 : 0) | (left > 2 ? in[i + 2] : 0);
+    out[o++] = a[v >> 18];
+    out[o++] = a[(v >> 12) & 63];
+    out[o++] = left > 1 ? a[(v >> 6) & 63] : '=';
+    out[o++] = left > 2 ? a[v & 63] : '=';
+  }
+  return o;
+}
+
+// "name:base64" of entry `at` of a values array (no line end, no NUL); returns its length.
+// CRC values are numbers, sent as big-endian bytes; digest words are the digest's bytes in memory.
+size_t trailer_line(const s3h::TrailerKind &K, const void *values, uint64_t at, char *out) {
+  uint8_t be[32];
+  if (K.value_len == 4) {
+    const uint32_t v = __builtin_bswap32(static_cast<const uint32_t *>(values)[at]);
+    std::memcpy(be, &v, 4);
+  } else if (K.value_len == 8) {
+    const uint64_t v = __builtin_bswap64(static_cast<const uint64_t *>(values)[at]);
+    std::memcpy(be, &v, 8);
+  } else {
+    std::memcpy(be, static_cast<const uint8_t *>(values) + K.value_len * at, K.value_len);
+  }
+  const size_t name = std::strlen(K.name);
+  std::memcpy(out, K.name, name);
+  out[name] = ':';
+  return name + 1 + base64(be, K.value_len, out + name + 1);
+}
+
+// The trailer link of one part: its checksum line hashed, then the HMAC over the trailer string.
+void trailer_link(const s3h_chunk_sign_ctx_s *C, const s3h::TrailerKind &K, const void *values, uint64_t at,
+                  const uint8_t *last, uint8_t *sig) {
+  uint8_t line[128] = {0};  // one block, or two for a SHA-256 checksum
+  size_t len = trailer_line(K, values, at, reinterpret_cast<char *>(line));
+  line[len++] = '\n';
+  line[len] = 0x80;
+  const size_t blocks = (len + 9 + 63) / 64;
+  line[64 * blocks - 2] = uint8_t((8 * len) >> 8);
+  line[64 * blocks - 1] = uint8_t(8 * len);
+  uint32_t st[8];
+  sha256::init_hash(st);
+  s3h::cpu::sha256_blocks(st, line, blocks);
+  uint8_t digest[32];
+  for (int i = 0; i < 8; ++i) {
+    const uint32_t be = __builtin_bswap32(st[i]);
+    std::memcpy(digest + 4 * i, &be, 4);
+  }
+  uint8_t tail[sizeof C->trailer_tail];
+  std::memcpy(tail, C->trailer_tail, 64 * C->trailer_nblk);
+  put_hex(last, 32, tail + C->r);
+  put_hex(digest, 32, tail + C->r + 65);
+  finish(C->trailer_istate, C->ostate, tail, C->trailer_nblk, sig);
 }
 
 void chain(const s3h_chunk_sign_ctx_s *C, const uint8_t *digests, uint64_t chunks, const uint8_t *seed,
@@ -76,6 +152,11 @@ void chain(const s3h_chunk_sign_ctx_s *C, const uint8_t *digests, uint64_t chunk
 }
 
 }  // namespace
+
+const s3h::TrailerKind *s3h::trailer_kind(int checksum) {
+  return checksum >= 0 && checksum < int(sizeof kTrailerKinds / sizeof kTrailerKinds[0]) ? &kTrailerKinds[checksum]
+                                                                                         : nullptr;
+}
 
 extern "C" {
 
@@ -115,11 +196,19 @@ int s3h_chunk_sign_ctx_create(const uint8_t key[32], const char *timestamp, cons
   C->r = C->prefix_len % 64;
   C->nblk = (C->r + 203 + 63) / 64;
 
+  // P': the same prefix under the trailer's algorithm name, 7 letters for 7 at byte 17
+  char tprefix[sizeof C->prefix];
+  std::memcpy(tprefix, C->prefix, C->prefix_len);
+  std::memcpy(tprefix + 17, "TRAILER", 7);
+  C->trailer_nblk = (C->r + 138 + 63) / 64;
+
   uint8_t pad[64];
   for (int i = 0; i < 64; ++i) pad[i] = uint8_t((i < 32 ? key[i] : 0) ^ 0x36);
   sha256::init_hash(C->istate);
   s3h::cpu::sha256_blocks(C->istate, pad, 1);
+  std::memcpy(C->trailer_istate, C->istate, sizeof C->istate);
   s3h::cpu::sha256_blocks(C->istate, reinterpret_cast<const uint8_t *>(C->prefix), C->prefix_len / 64);
+  s3h::cpu::sha256_blocks(C->trailer_istate, reinterpret_cast<const uint8_t *>(tprefix), C->prefix_len / 64);
   for (int i = 0; i < 64; ++i) pad[i] = uint8_t((i < 32 ? key[i] : 0) ^ 0x5c);
   sha256::init_hash(C->ostate);
   s3h::cpu::sha256_blocks(C->ostate, pad, 1);
@@ -137,6 +226,18 @@ int s3h_chunk_sign_ctx_create(const uint8_t key[32], const char *timestamp, cons
     uint32_t w;
     std::memcpy(&w, t + 4 * j, 4);
     C->tail_words[j] = __builtin_bswap32(w);
+  }
+  // the trailer tail: its prefix's last r bytes, [64 hex] '\n' [64 hex], 0x80, zeros, bit length
+  t = C->trailer_tail;
+  std::memcpy(t, tprefix + C->prefix_len - C->r, C->r);
+  t[C->r + 64] = '\n';
+  t[C->r + 129] = 0x80;
+  const uint64_t tbe = __builtin_bswap64(8ull * (64 + C->prefix_len + 129));
+  std::memcpy(t + 64 * C->trailer_nblk - 8, &tbe, 8);
+  for (int j = 0; j < s3h::kTrailerTailWords; ++j) {
+    uint32_t w;
+    std::memcpy(&w, t + 4 * j, 4);
+    C->trailer_tail_words[j] = __builtin_bswap32(w);
   }
   *out = C;
   return S3H_OK;
@@ -206,6 +307,60 @@ int s3h_chunk_header_text(uint64_t chunk_len, const uint32_t sig[8], char *out, 
   int at = std::snprintf(out, size_t(out_len), "%llx;chunk-signature=", static_cast<unsigned long long>(chunk_len));
   put_hex(reinterpret_cast<const uint8_t *>(sig), 32, reinterpret_cast<uint8_t *>(out) + at);
   std::memcpy(out + at + 64, "\r\n", 3);
+  return S3H_OK;
+}
+
+int s3h_cpu_trailer_signatures(s3h_chunk_sign_ctx_t ctx, int checksum, const void *values,
+                               const uint32_t *last_signatures, uint64_t n, uint32_t *trailer_signatures) {
+  const s3h::TrailerKind *K = s3h::trailer_kind(checksum);
+  if (!K) return fail(S3H_EINVAL, "trailer signatures: unknown checksum %d", checksum);
+  if (!ctx || !values || !last_signatures || !trailer_signatures || n == 0)
+    return fail(S3H_EINVAL, "trailer signatures: null argument or no parts");
+  const uint8_t *last = reinterpret_cast<const uint8_t *>(last_signatures);
+  uint8_t *sig = reinterpret_cast<uint8_t *>(trailer_signatures);
+  std::atomic<uint64_t> next{0};
+  auto work = [&] {  // 64 parts a turn: one link each
+    for (uint64_t i; (i = next.fetch_add(64)) < n;)
+      for (uint64_t k = i; k < std::min(n, i + 64); ++k) trailer_link(ctx, *K, values, k, last + 32 * k, sig + 32 * k);
+  };
+  int cpus = 1;
+  s3h_host_threads(1, &cpus);
+  const unsigned t = unsigned(std::min<uint64_t>(uint64_t(std::max(1, cpus)), (n + 63) / 64));
+  std::vector<std::thread> pool;
+  try {
+    for (unsigned k = 1; k < t; ++k) pool.emplace_back(work);
+  } catch (const std::exception &) {  // fewer threads: the ones started and this one finish
+  }
+  work();
+  for (auto &th : pool) th.join();
+  return S3H_OK;
+}
+
+int s3h_trailer_line_text(int checksum, const void *value, char *out, uint64_t out_len) {
+  if (out && out_len) out[0] = '\0';
+  const s3h::TrailerKind *K = s3h::trailer_kind(checksum);
+  if (!K) return fail(S3H_EINVAL, "trailer line text: unknown checksum %d", checksum);
+  if (!value || !out || out_len < S3H_TRAILER_LINE_MAX)
+    return fail(S3H_EINVAL, "trailer line text: need a value and %d output bytes", S3H_TRAILER_LINE_MAX);
+  static_assert(kTrailerLineMax < S3H_TRAILER_LINE_MAX, "the longest line and its NUL fit");
+  out[trailer_line(*K, value, 0, out)] = '\0';
+  return S3H_OK;
+}
+
+int s3h_chunk_trailer_text(int checksum, const void *value, const uint32_t trailer_sig[8], char *out,
+                           uint64_t out_len) {
+  if (out && out_len) out[0] = '\0';
+  const s3h::TrailerKind *K = s3h::trailer_kind(checksum);
+  if (!K) return fail(S3H_EINVAL, "chunk trailer text: unknown checksum %d", checksum);
+  if (!value || !trailer_sig || !out || out_len < S3H_CHUNK_TRAILER_MAX)
+    return fail(S3H_EINVAL, "chunk trailer text: need a value, a signature and %d output bytes",
+                S3H_CHUNK_TRAILER_MAX);
+  static_assert(kTrailerLineMax + 2 + 24 + 64 + 2 + 2 < S3H_CHUNK_TRAILER_MAX, "the longest trailer and its NUL fit");
+  size_t at = trailer_line(*K, value, 0, out);
+  std::memcpy(out + at, "\r\nx-amz-trailer-signature:", 26);
+  at += 26;
+  put_hex(reinterpret_cast<const uint8_t *>(trailer_sig), 32, reinterpret_cast<uint8_t *>(out) + at);
+  std::memcpy(out + at + 64, "\r\n\r\n", 5);
   return S3H_OK;
 }
 

@@ -3,7 +3,7 @@
 // unit with device code), pinned host memory and device placement (pinned.cpp), and the
 // stream units' hooks.  The C-ABI itself is include/s3hash.h.
 //
-//   launch.hip    sha256_kernels.hip + sha1_kernels.hip + crc32_kernels.hip + chunk_sign_kernels.hip + the hipLaunchKernelGGL calls (device code)
+//   launch.hip    sha256_kernels.hip + sha1_kernels.hip + crc32_kernels.hip + chunk_sign_kernels.hip + chunk_trailer_kernels.hip + the hipLaunchKernelGGL calls (device code)
 //   plan.cpp      plans: kernel choice, slot sorting, launches, error words; device-resident C-ABI
 //   pinned.cpp    NUMA-placed pinned host memory, device placement, s3h_host_alloc / _numa
 //   host_path.cpp host-resident pipeline (slices, groups), per-device contexts, the merge queue
@@ -11,7 +11,7 @@
 //   crc.cpp       CRC-32C / CRC-32 / CRC-64/NVME plans: whole-part and ranged launches (s3h_crc_*,
 //                 s3h_crc64nvme_*), the host path's plans
 //   chunk_sign.cpp SigV4 chunk-signed uploads: chunk plans and their launches (s3h_chunk_plan_*,
-//                 s3h_chunk_sign_batch_*); context and CPU chain: cpu/lib_chunk_sign.cpp
+//                 s3h_chunk_sign_batch_*, the trailer forms); context and CPU chain: cpu/lib_chunk_sign.cpp
 //   route.cpp     size-aware routing (model measurement, observed rates, routed entry points)
 //   HIP-free: status.cpp, topology.cpp, route_plan.cpp (+ copy_pool.hpp, host_queue.hpp)
 #pragma once
@@ -179,6 +179,8 @@ hipError_t launch_crc64_range(const s3h::Crc64Args& A, uint32_t piece_grid, hipS
 
 // The SigV4 chunk-signature chain (chunk_sign_kernels.hip): one lane per part, A.n parts.
 hipError_t launch_chunk_chain(const s3h::ChunkChainArgs& A, hipStream_t s);
+// The trailer signature behind it (chunk_trailer_kernels.hip): one lane per part, A.n parts.
+hipError_t launch_chunk_trailer(const s3h::ChunkTrailerArgs& A, hipStream_t s);
 
 // ------------------------------------------------------------------ CRC plans (crc.cpp)
 // The host path's use of a plan: created once per context with the tables uploaded

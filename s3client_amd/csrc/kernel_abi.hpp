@@ -200,6 +200,28 @@ struct ChunkChainArgs {
 };
 constexpr int kChunkChainThreads = 64;  // one wave per workgroup, one lane per part
 
+// ------------------------------------------------------------- SigV4 trailer signatures (chunk_trailer_kernels.hip)
+// The last link of a chunk-signed upload with a trailing checksum header
+// (STREAMING-AWS4-HMAC-SHA256-PAYLOAD-TRAILER): per part, the CRC as base64 in the header line,
+// the line's SHA-256, and the HMAC over the trailer string.  The parts are the chain kernel's
+// records: a part's last chunk signature is signatures[8 * (sig + count) ...].
+constexpr int kTrailerTailWords = 64;  // the inner tail: at most 4 blocks (r + 129 + 9 <= 201 bytes)
+struct ChunkTrailerArgs {
+  const uint32_t* signatures;  // the chunk signatures of the chain kernel
+  const ChunkChainPart* parts;
+  const void* checksums;       // n values in part order: uint32_t, or uint64_t when `wide`
+  uint32_t* trailer;           // n x 8 words, word i = bswap32(H_i)
+  uint64_t n;
+  uint32_t r;                  // |P| mod 64: the first hex field starts at tail byte r
+  uint32_t nblk;               // compressions of the inner tail (3 or 4)
+  uint32_t wide;               // 0: 32-bit values (8 characters), 1: 64-bit values (12)
+  uint32_t value_at;           // byte offset of the base64 text in the line
+  uint32_t istate[8];          // the trailer string's inner midstate
+  uint32_t ostate[8];
+  uint32_t line[16];           // the header line's one block, big-endian words, the value zeroed
+  uint32_t tail[kTrailerTailWords];  // big-endian words, the two 64-byte hex fields zeroed
+};
+
 // ------------------------------------------------------------- synthetic input generator
 // G(seed, p, L) of SURVEY.md 8(d): one record per part (byte offset, length, generator id).
 struct GenPart { uint64_t off, len, id; };

@@ -708,10 +708,15 @@ def chunk_header_text(chunk_len: int, signature) -> str:
 class ChunkSignPlan:
     """Device-resident parts cut into chunks of ``chunk_bytes``: a SHA-256 plan over the chunks
     plus each part's chain record (s3h_chunk_plan_create).  ``signature_offsets[p]`` is the row
-    of part p's first signature; part p has ``data_chunks_per_part[p] + 1`` of them."""
+    of part p's first signature; part p has ``data_chunks_per_part[p] + 1`` of them.
+
+    ``trailer`` = "crc32c", "crc32" or "crc64nvme" makes it a trailer plan
+    (s3h_chunk_plan_create_trailer, STREAMING-AWS4-HMAC-SHA256-PAYLOAD-TRAILER): it also owns a
+    CRC plan over the whole parts, and ``launch_trailer`` / ``trailer`` give each part's
+    checksum and trailer signature."""
 
     def __init__(self, offsets: Sequence[int], lengths: Sequence[int], chunk_bytes: int,
-                 device: int = 0):
+                 device: int = 0, trailer: str | None = None):
         self.offsets, self.lengths = _u64(offsets), _u64(lengths)
         if self.offsets.shape != self.lengths.shape or self.offsets.ndim != 1:
             raise ValueError("offsets and lengths must be 1-D and of equal length")
@@ -722,9 +727,15 @@ class ChunkSignPlan:
         self.data_chunks_per_part = g["data_chunks_per_part"]
         self.signature_offsets = g["signature_offsets"]
         self.signatures = g["signatures"]
+        self.trailer_kind = trailer
         h = ctypes.c_void_p()
-        check(lib().s3h_chunk_plan_create(device, _p64(self.offsets), _p64(self.lengths), self.n,
-                                          self.chunk_bytes, ctypes.byref(h)))
+        if trailer is None:
+            check(lib().s3h_chunk_plan_create(device, _p64(self.offsets), _p64(self.lengths), self.n,
+                                              self.chunk_bytes, ctypes.byref(h)))
+        else:
+            check(lib().s3h_chunk_plan_create_trailer(device, _trailer_id(trailer), _p64(self.offsets),
+                                                      _p64(self.lengths), self.n, self.chunk_bytes,
+                                                      ctypes.byref(h)))
         self._h = h
 
     def info(self) -> dict:
@@ -763,6 +774,43 @@ class ChunkSignPlan:
         check(lib().s3h_chunk_plan_chain(self._h, ctx._h, ctypes.c_void_p(chunk_digests.data_ptr()),
                                          ctypes.c_void_p(seeds.data_ptr()), ctypes.c_void_p(out.data_ptr()),
                                          ctypes.c_void_p(_stream_handle(stream))))
+
+    def _value_bytes(self) -> int:
+        if self.trailer_kind is None:
+            return 4  # (the library refuses the launch)
+        return np.dtype(_native.TRAILER_VALUE[_trailer_id(self.trailer_kind)][0]).itemsize
+
+    def launch_trailer(self, data, ctx: ChunkSignContext, seeds, out, checksums, trailer_out,
+                       stream=None) -> None:
+        """``launch``, then each part's CRC into ``checksums`` (n 32-bit words, or 64-bit for
+        crc64nvme) and its trailer signature into ``trailer_out`` (n x 8 words), all on
+        ``stream`` (s3h_chunk_plan_launch_trailer).  Device tensors, or raw device pointers."""
+        ptrs = []
+        for t, need in ((data, int((self.offsets + self.lengths).max()) if self.n else 0),
+                        (seeds, 32 * self.n), (out, 32 * self.signatures),
+                        (checksums, self._value_bytes() * self.n), (trailer_out, 32 * self.n)):
+            if isinstance(t, int):
+                ptrs.append(t)
+                continue
+            if not t.is_cuda:
+                raise ValueError("data, seeds and the outputs must be device tensors")
+            if t.numel() * t.element_size() < need:
+                raise ValueError(f"buffer of {t.numel() * t.element_size()} B, need {need} B")
+            ptrs.append(t.data_ptr())
+        check(lib().s3h_chunk_plan_launch_trailer(self._h, ctx._h, *(ctypes.c_void_p(p) for p in ptrs),
+                                                  ctypes.c_void_p(_stream_handle(stream))))
+
+    def trailer(self, ctx: ChunkSignContext, signatures, checksums, trailer_out, stream=None) -> None:
+        """The trailer kernel alone over chunk ``signatures`` (this plan's geometry) and
+        ``checksums`` already on the device (s3h_chunk_plan_trailer)."""
+        for t, need in ((signatures, 32 * self.signatures), (checksums, self._value_bytes() * self.n),
+                        (trailer_out, 32 * self.n)):
+            if not t.is_cuda or t.numel() * t.element_size() < need:
+                raise ValueError(f"need a device tensor of at least {need} B")
+        check(lib().s3h_chunk_plan_trailer(self._h, ctx._h, ctypes.c_void_p(signatures.data_ptr()),
+                                           ctypes.c_void_p(checksums.data_ptr()),
+                                           ctypes.c_void_p(trailer_out.data_ptr()),
+                                           ctypes.c_void_p(_stream_handle(stream))))
 
     def status(self, stream=None) -> None:
         """Wait for ``stream``; raise if a chunk-hash launch since the last check reported a
@@ -811,6 +859,98 @@ def chunk_sign_host(parts: Sequence, chunk_bytes: int, ctx: ChunkSignContext, se
     check(lib().s3h_chunk_sign_batch_host(ctx._h, ptrs, _p64(lens), n, int(chunk_bytes),
                                           sd.ctypes.data, out.ctypes.data))
     return out
+
+
+def _trailer_id(kind) -> int:
+    if isinstance(kind, str):
+        if kind not in _native.TRAILER_IDS:
+            raise ValueError(f"unknown trailer checksum {kind!r} (one of {sorted(_native.TRAILER_IDS)})")
+        return _native.TRAILER_IDS[kind]
+    return int(kind)
+
+
+def _trailer_values(kind, values, rows: int | None) -> np.ndarray:
+    """(rows,) or (rows, words) array of checksum values in the layout of ``kind``."""
+    dt, words = _native.TRAILER_VALUE[_trailer_id(kind)]
+    if isinstance(values, (bytes, bytearray, memoryview)):
+        values = np.frombuffer(values, dtype=np.uint8).view(dt)
+    a = np.ascontiguousarray(np.atleast_1d(values)).astype(dt, copy=False).reshape(-1, words)
+    if rows is not None and a.shape[0] != rows:
+        raise ValueError(f"checksum values: {a.shape[0]} entries, expected {rows}")
+    return a
+
+
+def cpu_trailer_signatures(ctx: ChunkSignContext, checksum, values, last_signatures) -> np.ndarray:
+    """The trailer link on the CPU (s3h_cpu_trailer_signatures): ``checksum`` "crc32c", "crc32",
+    "crc64nvme", "sha1" or "sha256", ``values`` n checksums in that kind's layout (numbers for
+    the CRCs, (n, 5) / (n, 8) words for the digests), ``last_signatures`` (n, 8): each part's
+    last chunk signature.  Returns (n, 8) uint32."""
+    last = _words(last_signatures, None, "last signatures")
+    n = last.shape[0]
+    vals = _trailer_values(checksum, values, n)
+    out = np.zeros((n, 8), dtype=np.uint32)
+    check(lib().s3h_cpu_trailer_signatures(ctx._h, _trailer_id(checksum), vals.ctypes.data,
+                                           last.ctypes.data, n, out.ctypes.data))
+    return out
+
+
+def trailer_line_text(checksum, value) -> str:
+    """The trailing header of one checksum value, "name:base64", no line end
+    (s3h_trailer_line_text)."""
+    vals = _trailer_values(checksum, value, 1)
+    buf = ctypes.create_string_buffer(_native.TRAILER_LINE_MAX)
+    check(lib().s3h_trailer_line_text(_trailer_id(checksum), vals.ctypes.data, buf, len(buf)))
+    return buf.value.decode()
+
+
+def chunk_trailer_text(checksum, value, trailer_signature) -> str:
+    """What follows the "0;chunk-signature=...\r\n" line: the trailing header, the
+    x-amz-trailer-signature line and the empty line (s3h_chunk_trailer_text)."""
+    vals = _trailer_values(checksum, value, 1)
+    sig = _words(trailer_signature, 1, "trailer signature")
+    buf = ctypes.create_string_buffer(_native.CHUNK_TRAILER_MAX)
+    check(lib().s3h_chunk_trailer_text(_trailer_id(checksum), vals.ctypes.data, sig.ctypes.data, buf,
+                                       len(buf)))
+    return buf.value.decode()
+
+
+def _trailer_outputs(kind, lens, chunk_bytes: int):
+    dt, words = _native.TRAILER_VALUE[_trailer_id(kind)]
+    n = int(lens.size)
+    sigs = np.zeros((chunk_geometry(lens, chunk_bytes)["signatures"], 8), dtype=np.uint32)
+    vals = np.zeros(n if words == 1 else (n, words), dtype=dt)
+    return sigs, vals, np.zeros((n, 8), dtype=np.uint32)
+
+
+def chunk_sign_trailer_batch_device(data, offsets, lengths, chunk_bytes: int, ctx: ChunkSignContext,
+                                    seeds, trailer: str = "crc32c"):
+    """One-shot: trailer plan, launch, copy back (s3h_chunk_sign_trailer_batch_device).  Returns
+    host (signatures, 8) uint32, the n checksums and (n, 8) uint32 trailer signatures."""
+    offs, lens = _u64(offsets), _u64(lengths)
+    n = int(lens.size)
+    sd = _words(seeds, n, "seeds")
+    sigs, vals, tsig = _trailer_outputs(trailer, lens, chunk_bytes)
+    check(lib().s3h_chunk_sign_trailer_batch_device(data.device.index or 0, ctx._h, _trailer_id(trailer),
+                                                    ctypes.c_void_p(data.data_ptr()), _p64(offs),
+                                                    _p64(lens), n, int(chunk_bytes), sd.ctypes.data,
+                                                    sigs.ctypes.data, vals.ctypes.data, tsig.ctypes.data))
+    return sigs, vals, tsig
+
+
+def chunk_sign_trailer_host(parts: Sequence, chunk_bytes: int, ctx: ChunkSignContext, seeds,
+                            trailer: str = "crc32c"):
+    """Host-resident parts: chunk digests and chunk CRCs from one pass through the host pipeline,
+    the CRCs folded per part, the chain and the trailer link on the CPU
+    (s3h_chunk_sign_trailer_batch_host; "sha1" / "sha256" hash the whole parts in a second
+    pass).  Returns (signatures, 8) uint32, the n checksums and (n, 8) trailer signatures."""
+    arrs, ptrs, lens = _host_parts(parts)
+    n = len(arrs)
+    sd = _words(seeds, n, "seeds")
+    sigs, vals, tsig = _trailer_outputs(trailer, lens, chunk_bytes)
+    check(lib().s3h_chunk_sign_trailer_batch_host(ctx._h, _trailer_id(trailer), ptrs, _p64(lens), n,
+                                                  int(chunk_bytes), sd.ctypes.data, sigs.ctypes.data,
+                                                  vals.ctypes.data, tsig.ctypes.data))
+    return sigs, vals, tsig
 
 
 class Crc64Plan(CrcPlan):

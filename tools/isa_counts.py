@@ -65,6 +65,8 @@ ALL_KERNELS = {
     "sha1-pc": KERNELS["sha1-pc"][0], "sha1-pc1": KERNELS["sha1-pc1"][0],
     # SigV4 chunk-signature chain (chunk_sign_kernels.hip): code hash only
     "chunk-chain": "_ZN3s3h24sigv4_chunk_chain_kernelENS_14ChunkChainArgsE",
+    # SigV4 trailer signature (chunk_trailer_kernels.hip): code hash only
+    "chunk-trailer": "_ZN3s3h20sigv4_trailer_kernelENS_16ChunkTrailerArgsE",
 }
 FLAG_KERNELS = ("skew_nc2", "skews", "dual_group", "dual_group_skew", "dual_group_mixed")
 ERR_STORE = re.compile(r"^\t(global|flat|buffer)_atomic_or\b")
