@@ -484,9 +484,17 @@ int s3h_sha256_md5_file_parts_routed(const char *path, const uint64_t *offsets,
 
 /* ---------------------------------------------------------------- verification
  * Download-side check of parts against known digests (ranged GETs of
- * lib/src/download.cpp:88-103; expected = the uploader's x-amz-content-sha256 / Content-MD5).
- * mismatch[i] = 1 when part i differs; *mismatches = their count.  Blocking.
- * Device form: d_expected (n x words) and d_mismatch (n bytes) are device pointers. */
+ * lib/src/download.cpp:88-103; expected = the uploader's x-amz-content-sha256 / Content-MD5 /
+ * x-amz-checksum-sha1).  `expected` holds n x words 32-bit words in the layout the batch calls
+ * write: 8 per part for S3H_ALGO_SHA256, 4 for S3H_ALGO_MD5, 5 for S3H_ALGO_SHA1; every word is
+ * compared.  A successful call writes all n bytes of `mismatch`, whatever they held: mismatch[i]
+ * = 1 when part i differs, 0 when it matches (an empty part matches the digest of the empty
+ * message); no byte behind mismatch[n - 1] is touched; *mismatches is stored (not added to) and
+ * equals the sum of the n bytes.  The CRC forms (s3h_crc_verify_batch_device,
+ * s3h_crc64nvme_verify_batch_device) keep the same contract with 1 and 2 words per value.
+ * Blocking.  Device form: d_expected (n x words, 4-byte aligned) and d_mismatch (n bytes) are
+ * device pointers; the comparison runs on `stream`, behind work queued there earlier (such as
+ * a launch that is still writing d_expected). */
 int s3h_verify_batch_device(int device, int algo, const void *d_base, const uint64_t *offsets,
                             const uint64_t *lengths, uint64_t n, const uint32_t *d_expected,
                             uint8_t *d_mismatch, uint64_t *mismatches, void *stream);

@@ -366,23 +366,19 @@ int s3h_crc_verify_batch_device(int device, int crc, const void* d_base, const u
   } cleanup{P};
   DeviceGuard g(device);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  uint32_t* d_crcs = nullptr;
-  unsigned long long* d_count = nullptr;
-  HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&d_crcs), n * 4, s));
-  HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&d_count), 8, s));
-  HIP_TRY(hipMemsetAsync(d_count, 0, 8, s));
-  int rc = crc_plan_launch(P, d_base, d_crcs, s);
+  VerifyScratch scratch(s);  // freed on every return below
+  HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&scratch.values), n * 4, s));
+  HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&scratch.count), 8, s));
+  HIP_TRY(hipMemsetAsync(scratch.count, 0, 8, s));
+  int rc = crc_plan_launch(P, d_base, scratch.values, s);
   if (rc == S3H_OK) {
     unsigned long long c = 0;
-    hipError_t e = launch_compare_digests(d_crcs, d_expected, n, 1, d_mismatch, d_count, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(&c, d_count, 8, hipMemcpyDeviceToHost, s);
+    hipError_t e = launch_compare_digests(scratch.values, d_expected, n, 1, d_mismatch, scratch.count, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(&c, scratch.count, 8, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) rc = fail(S3H_EHIP, "crc verify: %s", hipGetErrorString(e));
     *mismatches = c;
   }
-  (void)hipFreeAsync(d_crcs, s);
-  (void)hipFreeAsync(d_count, s);
-  (void)hipStreamSynchronize(s);
   return rc;
 }
 
@@ -456,24 +452,20 @@ int s3h_crc64nvme_verify_batch_device(int device, const void* d_base, const uint
   } cleanup{P};
   DeviceGuard g(device);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  uint32_t* d_crcs = nullptr;
-  unsigned long long* d_count = nullptr;
-  HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&d_crcs), n * 8, s));
-  HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&d_count), 8, s));
-  HIP_TRY(hipMemsetAsync(d_count, 0, 8, s));
-  int rc = crc_plan_launch(P, d_base, d_crcs, s);
+  VerifyScratch scratch(s);  // freed on every return below
+  HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&scratch.values), n * 8, s));
+  HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&scratch.count), 8, s));
+  HIP_TRY(hipMemsetAsync(scratch.count, 0, 8, s));
+  int rc = crc_plan_launch(P, d_base, scratch.values, s);
   if (rc == S3H_OK) {
     unsigned long long c = 0;
-    hipError_t e = launch_compare_digests(d_crcs, reinterpret_cast<const uint32_t*>(d_expected), n, 2,
-                                          d_mismatch, d_count, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(&c, d_count, 8, hipMemcpyDeviceToHost, s);
+    hipError_t e = launch_compare_digests(scratch.values, reinterpret_cast<const uint32_t*>(d_expected), n, 2,
+                                          d_mismatch, scratch.count, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(&c, scratch.count, 8, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) rc = fail(S3H_EHIP, "crc64nvme verify: %s", hipGetErrorString(e));
     *mismatches = c;
   }
-  (void)hipFreeAsync(d_crcs, s);
-  (void)hipFreeAsync(d_count, s);
-  (void)hipStreamSynchronize(s);
   return rc;
 }
 

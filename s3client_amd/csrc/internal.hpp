@@ -114,6 +114,25 @@ struct DeviceGuard {  // restores the calling thread's current device
   DeviceGuard& operator=(const DeviceGuard&) = delete;
 };
 
+// Stream-ordered scratch of one blocking verification call (the computed values and the
+// mismatch counter): freed on `s`, which is then drained, on every return path -- a failed
+// second allocation or memset included.  Declared after the call's DeviceGuard, so that it
+// frees on the call's device.
+struct VerifyScratch {
+  hipStream_t s;
+  uint32_t* values = nullptr;
+  unsigned long long* count = nullptr;
+  explicit VerifyScratch(hipStream_t stream) : s(stream) {}
+  ~VerifyScratch() {
+    if (!values && !count) return;
+    if (values) (void)hipFreeAsync(values, s);
+    if (count) (void)hipFreeAsync(count, s);
+    (void)hipStreamSynchronize(s);
+  }
+  VerifyScratch(const VerifyScratch&) = delete;
+  VerifyScratch& operator=(const VerifyScratch&) = delete;
+};
+
 // ------------------------------------------------------------------ plans (plan.cpp)
 constexpr uint64_t kMaxParts = 1ull << 31;
 int device_cus(int device);  // cached CU count (0 if unknown)

@@ -717,24 +717,20 @@ int s3h_verify_batch_device(int device, int algo, const void* d_base, const uint
   DeviceGuard g(device);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const uint32_t dw = digest_words(algo);
-  uint32_t* d_dig = nullptr;
-  unsigned long long* d_count = nullptr;
-  HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&d_dig), n * dw * 4, s));
-  HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&d_count), 8, s));
-  HIP_TRY(hipMemsetAsync(d_count, 0, 8, s));
-  int rc = plan_launch(P, d_base, d_dig, 0, P->max_blocks, 0, s, false);
+  VerifyScratch scratch(s);  // freed on every return below
+  HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&scratch.values), n * dw * 4, s));
+  HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&scratch.count), 8, s));
+  HIP_TRY(hipMemsetAsync(scratch.count, 0, 8, s));
+  int rc = plan_launch(P, d_base, scratch.values, 0, P->max_blocks, 0, s, false);
   if (rc == S3H_OK) {
     unsigned long long c = 0;
-    hipError_t e = launch_compare_digests(d_dig, d_expected, n, dw, d_mismatch, d_count, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(&c, d_count, 8, hipMemcpyDeviceToHost, s);
+    hipError_t e = launch_compare_digests(scratch.values, d_expected, n, dw, d_mismatch, scratch.count, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(&c, scratch.count, 8, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) rc = fail(S3H_EHIP, "verify: %s", hipGetErrorString(e));
     else rc = plan_check(P, s);  // a faulted launch verifies nothing
     *mismatches = c;
   }
-  (void)hipFreeAsync(d_dig, s);
-  (void)hipFreeAsync(d_count, s);
-  (void)hipStreamSynchronize(s);
   return rc;
 }
 

@@ -285,7 +285,9 @@ def md5_batch_host(parts: Sequence, ndevices: int = 0, slice_bytes: int = 0) -> 
 def verify_batch_host(parts: Sequence, expected, algo: str = "sha256",
                       ndevices: int = 0) -> np.ndarray:
     """Download-side verification: bool mask of parts whose digest differs from ``expected``
-    ((n, 8) uint32 SHA-256 or (n, 4) MD5 words, or a list of hex strings)."""
+    ((n, 8) uint32 SHA-256, (n, 4) MD5 or (n, 5) SHA-1 words for ``algo`` "sha256" / "md5" /
+    "sha1", or a list of hex strings).  Every word is compared.  The library writes all n mask
+    bytes, 0 or 1, nothing behind them, and a count equal to their sum (s3h_verify_batch_host)."""
     a = _native.ALGO_IDS[algo]
     words = _native.DIGEST_WORDS[a]
     if len(expected) and isinstance(expected[0], str):
