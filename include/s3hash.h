@@ -228,7 +228,13 @@ int s3h_plan_algo(s3h_plan_t plan);
 int s3h_plan_destroy(s3h_plan_t plan);
 /* Asynchronous on `stream`: d_base and d_digests (n*8 uint32) are device pointers.  The
  * launch's success is known only after it has run: call s3h_plan_status before using the
- * digests. */
+ * digests.
+ * Alignment of d_digests, here and in every device entry point that takes SHA-256 or MD5
+ * digests (s3h_plan_launch / _launch_range, s3h_sha256_batch_device, s3h_md5_batch_device,
+ * d_sha256 and d_md5 of s3h_sha256_md5_batch_device, s3h_stream_final_device): 16 bytes, the
+ * kernels store a digest as one or two 16-byte words.  SHA-1 digests (5 words): 4 bytes.
+ * d_base and the offsets may have any byte alignment.  A pointer that misses its alignment is
+ * S3H_EINVAL, before anything is allocated or launched. */
 int s3h_plan_launch(s3h_plan_t plan, const void *d_base, uint32_t *d_digests, void *stream);
 /* Waits for `stream`, then reads and clears the plan's device error word, which every launch
  * of the plan (s3h_plan_launch / _range) ORs its faults into.  S3H_OK: the digests of every
@@ -274,13 +280,14 @@ int s3h_dual_layout(const uint64_t *lengths, uint64_t n, int cus, uint32_t *solo
  * the probe off.  bench.py uses it to report cycles per block and the live shader clock. */
 int s3h_plan_set_clock_probe(s3h_plan_t plan, uint64_t *d_clocks, uint32_t *waves);
 
-/* One-shot convenience: plan + launch + wait.  Returns when d_digests is complete. */
+/* One-shot convenience: plan + launch + wait.  Returns when d_digests (16-byte aligned) is
+ * complete. */
 int s3h_sha256_batch_device(int device, const void *d_base, const uint64_t *offsets,
                             const uint64_t *lengths, uint64_t n, uint32_t *d_digests,
                             void *stream);
 
 /* Batched MD5 (lib/hash/md5.cpp semantics with md5_file's padding): n x 4 words, the
- * digest bytes in memory order (md5::hash_to_text prints them). */
+ * digest bytes in memory order (md5::hash_to_text prints them).  d_digests: 16-byte aligned. */
 int s3h_md5_batch_device(int device, const void *d_base, const uint64_t *offsets,
                          const uint64_t *lengths, uint64_t n, uint32_t *d_digests, void *stream);
 
@@ -348,6 +355,8 @@ int s3h_md5_file_parts(const char *path, const uint64_t *offsets, const uint64_t
 int s3h_sha256_md5_file_parts(const char *path, const uint64_t *offsets, const uint64_t *lengths,
                               uint64_t n, uint32_t *sha256_digests, uint32_t *md5_digests,
                               int ndevices, uint64_t slice_bytes);
+/* Device form: d_sha256 and d_md5 are device pointers, each 16-byte aligned (S3H_EINVAL if
+ * not).  The work runs on `stream`; the call returns when both are complete. */
 int s3h_sha256_md5_batch_device(int device, const void *d_base, const uint64_t *offsets,
                                 const uint64_t *lengths, uint64_t n, uint32_t *d_sha256,
                                 uint32_t *d_md5, void *stream);
@@ -522,7 +531,8 @@ int s3h_verify_batch_routed(int algo, const uint8_t *const *parts, const uint64_
  *           stream reaches this point.  An object's calls run on the device in call order,
  *           whichever stream each is given (each waits for the previous call's work).
  *   final:  pads every message with its total length, writes n digests (words as in the
- *           batch API) and resets the object to n empty messages.
+ *           batch API) and resets the object to n empty messages.  d_digests of the device
+ *           form is 16-byte aligned for SHA-256 and MD5, 4-byte for SHA-1 (S3H_EINVAL if not).
  * The chaining state, carries and total lengths live on the device (n x 104 B); one object
  * may be driven from one host thread at a time.  MD5 (algo 1) follows md5_stream/md5_file. */
 typedef struct s3h_stream_s *s3h_stream_t;
@@ -572,7 +582,8 @@ enum s3h_crc { S3H_CRC32C = 0, S3H_CRC32 = 1 };
 typedef struct s3h_crc_plan_s *s3h_crc_plan_t;
 int s3h_crc_plan_create(int device, int crc, const uint64_t *offsets, const uint64_t *lengths,
                         uint64_t n, s3h_crc_plan_t *plan);
-/* Asynchronous on `stream`: d_crcs (n words, device) is complete when the stream reaches it. */
+/* Asynchronous on `stream`: d_crcs (n words, device, 4-byte aligned) is complete when the
+ * stream reaches it. */
 int s3h_crc_plan_launch(s3h_crc_plan_t plan, const void *d_base, uint32_t *d_crcs, void *stream);
 /* Resumable form (as s3h_plan_launch_range, in bytes): process bytes [byte_begin, byte_end) of
  * every part, where part p's byte b lives at d_base + offsets[p] + (b - byte_origin).  Each

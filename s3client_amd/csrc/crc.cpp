@@ -301,6 +301,7 @@ int s3h_crc_plan_create(int device, int crc, const uint64_t* offsets, const uint
 
 int s3h_crc_plan_launch(s3h_crc_plan_t P, const void* d_base, uint32_t* d_crcs, void* stream) {
   if (!P || !d_base || !d_crcs) return fail(S3H_EINVAL, "crc launch: null argument");
+  if (misaligned(d_crcs, 4)) return fail(S3H_EINVAL, "crc launch: crcs must be 4-byte aligned");
   return crc_plan_launch(P, d_base, d_crcs, static_cast<hipStream_t>(stream));
 }
 
@@ -308,6 +309,7 @@ int s3h_crc_plan_launch_range(s3h_crc_plan_t P, const void* d_base, uint32_t* d_
                               uint64_t byte_begin, uint64_t byte_end, uint64_t byte_origin,
                               void* stream) {
   if (!P || !d_base || !d_crcs) return fail(S3H_EINVAL, "crc range launch: null argument");
+  if (misaligned(d_crcs, 4)) return fail(S3H_EINVAL, "crc range launch: crcs must be 4-byte aligned");
   return crc_plan_launch_range(P, d_base, d_crcs, byte_begin, byte_end, byte_origin,
                                static_cast<hipStream_t>(stream));
 }
@@ -339,6 +341,7 @@ int s3h_crc_batch_device(int device, int crc, const void* d_base, const uint64_t
                          const uint64_t* lengths, uint64_t n, uint32_t* d_crcs, void* stream) {
   if (int rc = check_crc_args(crc, offsets, lengths, n)) return rc;
   if (!d_base || !d_crcs) return fail(S3H_EINVAL, "crc batch: null argument");
+  if (misaligned(d_crcs, 4)) return fail(S3H_EINVAL, "crc batch: crcs must be 4-byte aligned");
   s3h_crc_plan_s* P = nullptr;
   if (int rc = crc_plan_build(device, crc, offsets, lengths, n, &P)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -358,6 +361,7 @@ int s3h_crc_verify_batch_device(int device, int crc, const void* d_base, const u
   if (int rc = check_crc_args(crc, offsets, lengths, n)) return rc;
   if (!d_base || !d_expected || !d_mismatch || !mismatches)
     return fail(S3H_EINVAL, "crc verify: null argument");
+  if (misaligned(d_expected, 4)) return fail(S3H_EINVAL, "crc verify: expected must be 4-byte aligned");
   s3h_crc_plan_s* P = nullptr;
   if (int rc = crc_plan_build(device, crc, offsets, lengths, n, &P)) return rc;
   struct Cleanup {
@@ -397,6 +401,7 @@ int s3h_crc64nvme_plan_create(int device, const uint64_t* offsets, const uint64_
 
 int s3h_crc64nvme_plan_launch(s3h_crc64nvme_plan_t H, const void* d_base, uint64_t* d_crcs, void* stream) {
   if (!H || !d_base || !d_crcs) return fail(S3H_EINVAL, "crc64nvme launch: null argument");
+  if (misaligned(d_crcs, 8)) return fail(S3H_EINVAL, "crc64nvme launch: crcs must be 8-byte aligned");
   return crc_plan_launch(H->p, d_base, reinterpret_cast<uint32_t*>(d_crcs), static_cast<hipStream_t>(stream));
 }
 
@@ -404,6 +409,7 @@ int s3h_crc64nvme_plan_launch_range(s3h_crc64nvme_plan_t H, const void* d_base, 
                                     uint64_t byte_begin, uint64_t byte_end, uint64_t byte_origin,
                                     void* stream) {
   if (!H || !d_base || !d_crcs) return fail(S3H_EINVAL, "crc64nvme range launch: null argument");
+  if (misaligned(d_crcs, 8)) return fail(S3H_EINVAL, "crc64nvme range launch: crcs must be 8-byte aligned");
   return crc_plan_launch_range(H->p, d_base, reinterpret_cast<uint32_t*>(d_crcs), byte_begin, byte_end,
                                byte_origin, static_cast<hipStream_t>(stream));
 }
@@ -425,6 +431,7 @@ int s3h_crc64nvme_batch_device(int device, const void* d_base, const uint64_t* o
                                const uint64_t* lengths, uint64_t n, uint64_t* d_crcs, void* stream) {
   if (int rc = check_batch_args(offsets, lengths, n)) return rc;
   if (!d_base || !d_crcs) return fail(S3H_EINVAL, "crc64nvme batch: null argument");
+  if (misaligned(d_crcs, 8)) return fail(S3H_EINVAL, "crc64nvme batch: crcs must be 8-byte aligned");
   s3h_crc_plan_s* P = nullptr;
   if (int rc = crc_plan_build(device, kCrcIdCrc64Nvme, offsets, lengths, n, &P)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -444,6 +451,7 @@ int s3h_crc64nvme_verify_batch_device(int device, const void* d_base, const uint
   if (int rc = check_batch_args(offsets, lengths, n)) return rc;
   if (!d_base || !d_expected || !d_mismatch || !mismatches)
     return fail(S3H_EINVAL, "crc64nvme verify: null argument");
+  if (misaligned(d_expected, 4)) return fail(S3H_EINVAL, "crc64nvme verify: expected must be 4-byte aligned");
   s3h_crc_plan_s* P = nullptr;
   if (int rc = crc_plan_build(device, kCrcIdCrc64Nvme, offsets, lengths, n, &P)) return rc;
   struct Cleanup {

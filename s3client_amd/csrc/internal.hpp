@@ -101,6 +101,13 @@ namespace s3h::host {
 
 int check_device(int device);
 
+// Alignment the C-ABI asks of a caller's digest pointer (include/s3hash.h): the SHA-256 and MD5
+// kernels store a digest through uint4 (16 bytes), the SHA-1 kernel stores dwords.
+inline unsigned digest_align(int algo) { return algo == S3H_ALGO_SHA1 ? 4u : 16u; }
+inline bool misaligned(const void* p, unsigned bytes) {
+  return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) != 0;
+}
+
 struct DeviceGuard {  // restores the calling thread's current device
   int prev = -1;
   explicit DeviceGuard(int dev) {

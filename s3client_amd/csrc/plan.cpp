@@ -502,8 +502,17 @@ uint32_t consumer_groups(const s3h_plan_s* P) {
                                                                           : 0u;
 }
 
+// S3H_EINVAL for a caller's digest pointer that misses the alignment the header states for
+// `algo` (the kernels' uint4 / dword stores would fault or tear on it).
+int check_digest_ptr(int algo, const void* d_digests, const char* what) {
+  if (misaligned(d_digests, digest_align(algo)))
+    return fail(S3H_EINVAL, "%s: digests must be %u-byte aligned", what, digest_align(algo));
+  return S3H_OK;
+}
+
 int batch_device(int device, int algo, const void* d_base, const uint64_t* offsets,
                  const uint64_t* lengths, uint64_t n, uint32_t* d_digests, void* stream) {
+  if (int rc = check_digest_ptr(algo, d_digests, "batch")) return rc;  // before any allocation
   s3h_plan_s* P = nullptr;
   if (int rc = plan_build(device, algo, offsets, lengths, n, S3H_KERNEL_AUTO, &P)) return rc;
   int rc = plan_launch(P, d_base, d_digests, 0, P->max_blocks, 0, static_cast<hipStream_t>(stream), false);
@@ -590,6 +599,7 @@ int s3h_plan_status(s3h_plan_t P, void* stream) {
 
 int s3h_plan_launch(s3h_plan_t P, const void* d_base, uint32_t* d_digests, void* stream) {
   if (!P) return fail(S3H_EINVAL, "null plan");
+  if (int rc = check_digest_ptr(P->algo, d_digests, "launch")) return rc;
   return plan_launch(P, d_base, d_digests, 0, P->max_blocks, 0, static_cast<hipStream_t>(stream), false);
 }
 
@@ -598,6 +608,7 @@ int s3h_plan_launch_range(s3h_plan_t P, const void* d_base, uint32_t* d_digests,
   if (!P) return fail(S3H_EINVAL, "null plan");
   if (origin > b0) return fail(S3H_EINVAL, "blk_origin (%llu) > blk_begin (%llu)",
                                (unsigned long long)origin, (unsigned long long)b0);
+  if (int rc = check_digest_ptr(P->algo, d_digests, "launch range")) return rc;
   return plan_launch(P, d_base, d_digests, b0, b1, origin, static_cast<hipStream_t>(stream), true);
 }
 
@@ -672,6 +683,8 @@ int s3h_sha256_md5_batch_device(int device, const void* d_base, const uint64_t* 
                                 const uint64_t* lengths, uint64_t n, uint32_t* d_sha256,
                                 uint32_t* d_md5, void* stream) {
   if (!d_base || !d_sha256 || !d_md5) return fail(S3H_EINVAL, "dual batch: null pointer");
+  if (int rc = check_digest_ptr(S3H_ALGO_SHA256, d_sha256, "dual batch SHA-256")) return rc;
+  if (int rc = check_digest_ptr(S3H_ALGO_MD5, d_md5, "dual batch MD5")) return rc;
   s3h_plan_s* P[2] = {};
   struct Cleanup {
     s3h_plan_s** P;
@@ -708,6 +721,7 @@ int s3h_verify_batch_device(int device, int algo, const void* d_base, const uint
                             const uint64_t* lengths, uint64_t n, const uint32_t* d_expected,
                             uint8_t* d_mismatch, uint64_t* mismatches, void* stream) {
   if (!d_expected || !d_mismatch || !mismatches) return fail(S3H_EINVAL, "verify: null argument");
+  if (misaligned(d_expected, 4)) return fail(S3H_EINVAL, "verify: expected must be 4-byte aligned");
   s3h_plan_s* P = nullptr;
   if (int rc = plan_build(device, algo, offsets, lengths, n, S3H_KERNEL_AUTO, &P)) return rc;
   struct Cleanup {
@@ -738,6 +752,7 @@ int s3h_generate_parts(int device, void* d_base, const uint64_t* offsets, const 
                        const uint64_t* part_ids, uint64_t n, uint64_t seed, void* stream) {
   if (!d_base || !offsets || !lengths || !part_ids || n == 0 || n > 65535)
     return fail(S3H_EINVAL, "generate: bad arguments (n must be in [1, 65535] per call)");
+  if (misaligned(d_base, 8)) return fail(S3H_EINVAL, "generate: d_base must be 8-byte aligned");
   if (int rc = check_device(device)) return rc;
   std::vector<s3h::GenPart> g(n);
   uint64_t maxlen = 0;

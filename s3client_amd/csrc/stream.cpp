@@ -444,6 +444,8 @@ int s3h_stream_update_device(s3h_stream_t S, const void* d_base, const uint64_t*
 
 int s3h_stream_final_device(s3h_stream_t S, uint32_t* d_digests, void* stream) {
   if (!S || !d_digests) return fail(S3H_EINVAL, "stream final: null argument");
+  if (misaligned(d_digests, digest_align(S->algo)))
+    return fail(S3H_EINVAL, "stream final: digests must be %u-byte aligned", digest_align(S->algo));
   DeviceGuard g(S->device);
   return stream_final(S, d_digests, static_cast<hipStream_t>(stream));
 }

@@ -63,6 +63,51 @@ def _stream_handle(stream) -> int | None:
     return getattr(stream, "cuda_stream", stream)
 
 
+def _device_buffer(name: str, t, need: int, device: int | None = None, align: int = 1,
+                   raw: bool = False) -> ctypes.c_void_p:
+    """The one gate between a caller's tensor and a device pointer handed to the library: every
+    device wrapper below passes each of its tensors through here and gives ``lib()`` only what
+    this returns.  The kernels read and write ``need`` contiguous bytes from ``data_ptr()``, so
+    anything else would give wrong digests with status OK.  Raises ValueError naming ``name``
+    when ``t``
+      * is not a device tensor (a host tensor, a numpy array),
+      * is on another device than ``device`` (the plan's, stream object's or ``device=``),
+      * is not contiguous (``buf[::2]``, a transposed tensor, a column slice ``pool[:, :8]``),
+      * holds fewer than ``need`` bytes,
+      * starts at an address that misses ``align``, the alignment include/s3hash.h states for
+        that argument (16 B for SHA-256 / MD5 digests, seeds and signatures; 8 B for 64-bit
+        values; 4 B for SHA-1 digests, 32-bit values and expected words; data: any).
+    The element type does not matter (bytes are bytes), nor does a storage offset.  With
+    ``raw`` a plain int is taken as a raw device pointer the caller vouches for: the library
+    itself checks its alignment.  O(1): no device work, no synchronisation."""
+    if raw and isinstance(t, int):
+        return ctypes.c_void_p(t)
+    if not getattr(t, "is_cuda", False):
+        raise ValueError(f"{name} must be a device tensor")
+    if device is not None and t.device.index != device:
+        raise ValueError(f"{name} is on device {t.device.index}, the call runs on device {device}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous: the kernels address {need} consecutive "
+                         "bytes from data_ptr(), not the tensor's strides")
+    have = t.numel() * t.element_size()
+    if have < need:
+        raise ValueError(f"{name} buffer too small ({have} B, need {need} B)")
+    ptr = t.data_ptr()
+    if align > 1 and ptr % align:
+        raise ValueError(f"{name} must be {align}-byte aligned (data_ptr() % {align} = {ptr % align})")
+    return ctypes.c_void_p(ptr)
+
+
+def _digest_align(algo: int) -> int:
+    # the SHA-256 and MD5 kernels store a digest as 16-byte words, SHA-1 as dwords
+    return 4 if algo == _native.ALGO_IDS["sha1"] else 16
+
+
+def _extent(offs: np.ndarray, lens: np.ndarray) -> int:
+    """Bytes of the data buffer that parts (offs, lens) reach."""
+    return int((offs + lens).max()) if offs.size else 0
+
+
 class Plan:
     """Geometry of one batch of parts, uploaded once (s3h_plan_create)."""
 
@@ -101,30 +146,23 @@ class Plan:
         per wave, s_memtime / s_memrealtime); None switches the probe off.  Returns the
         number of consumer waves that record (0 if the plan's kernel does not)."""
         w = ctypes.c_uint32()
-        ptr = ctypes.c_void_p(clocks.data_ptr() if clocks is not None else None)
+        ptr = (None if clocks is None else
+               _device_buffer("clock buffer", clocks, 0, self.device, align=8))
         check(lib().s3h_plan_set_clock_probe(self._h, ptr, ctypes.byref(w)))
-        if clocks is not None and clocks.numel() < 4 * w.value:
+        if clocks is not None and clocks.numel() * clocks.element_size() < 32 * w.value:
             lib().s3h_plan_set_clock_probe(self._h, None, None)
             raise ValueError(f"clock buffer needs {4 * w.value} int64 entries")
         return w.value
 
-    def _check_buffers(self, data, digests):
-        import torch
-        if not (data.is_cuda and digests.is_cuda):
-            raise ValueError("data and digests must be device tensors")
-        if digests.numel() * digests.element_size() < 4 * self.words * self.n:
-            raise ValueError(f"digests buffer too small (need n*{4 * self.words} bytes)")
-        end = int((self.offsets + self.lengths).max()) if self.n else 0
-        if data.numel() * data.element_size() < end:
-            raise ValueError(f"data buffer ({data.numel() * data.element_size()} B) smaller "
-                             f"than the plan's extent ({end} B)")
-        del torch
+    def _digests_ptr(self, digests) -> ctypes.c_void_p:
+        return _device_buffer("digests", digests, 4 * self.words * self.n, self.device,
+                              align=_digest_align(self.algo))
 
     def launch(self, data, digests, stream=None) -> None:
-        """Hash every part of ``data`` (device tensor) into ``digests`` (n*8 words)."""
-        self._check_buffers(data, digests)
-        check(lib().s3h_plan_launch(self._h, ctypes.c_void_p(data.data_ptr()),
-                                    ctypes.c_void_p(digests.data_ptr()),
+        """Hash every part of ``data`` (device tensor) into ``digests`` (n*8 words; contiguous,
+        16-byte aligned for SHA-256 and MD5, 4-byte for SHA-1).  Asynchronous on ``stream``."""
+        d_base = _device_buffer("data", data, _extent(self.offsets, self.lengths), self.device)
+        check(lib().s3h_plan_launch(self._h, d_base, self._digests_ptr(digests),
                                     ctypes.c_void_p(_stream_handle(stream))))
 
     def status(self, stream=None) -> None:
@@ -136,7 +174,7 @@ class Plan:
     def launch_range(self, data_ptr: int, digests, blk_begin: int, blk_end: int,
                      blk_origin: int, stream=None) -> None:
         check(lib().s3h_plan_launch_range(self._h, ctypes.c_void_p(data_ptr),
-                                          ctypes.c_void_p(digests.data_ptr()), blk_begin,
+                                          self._digests_ptr(digests), blk_begin,
                                           blk_end, blk_origin,
                                           ctypes.c_void_p(_stream_handle(stream))))
 
@@ -165,6 +203,7 @@ def sha256_batch_device(data, offsets, lengths, device: int | None = None, kerne
     Returns an (n, 8) int32 device tensor holding the uint32 digest words (lib/hash layout);
     (n, 4) for algo="md5"."""
     import torch
+    _device_buffer("data", data, 0, device)  # (a host tensor has no device to plan for)
     dev = data.device.index if device is None else device
     with Plan(offsets, lengths, device=dev, kernel=kernel, algo=algo) as plan:
         out = torch.empty((plan.n, plan.words), dtype=torch.int32, device=data.device)
@@ -262,17 +301,18 @@ def sha256_md5_batch_device(data, offsets, lengths, device: int | None = None, s
     (s3h_sha256_md5_batch_device): one grid running both chains while the batch fits one
     workgroup per CU, above that the two kernels one after the other on ``stream``."""
     import torch
+    _device_buffer("data", data, 0, device)
     dev = data.device.index if device is None else device
     offs, lens = _u64(offsets), _u64(lengths)
     if offs.shape != lens.shape:
         raise ValueError("offsets and lengths differ in length")
     n = int(lens.size)
-    if n and int((offs + lens).max()) > data.numel() * data.element_size():
-        raise ValueError("a part extends past the end of the data tensor")
+    d_base = _device_buffer("data", data, _extent(offs, lens), dev)
     sha = torch.empty((n, 8), dtype=torch.int32, device=data.device)
     m5 = torch.empty((n, 4), dtype=torch.int32, device=data.device)
-    check(lib().s3h_sha256_md5_batch_device(dev, data.data_ptr(), _p64(offs), _p64(lens), n,
-                                            sha.data_ptr(), m5.data_ptr(),
+    check(lib().s3h_sha256_md5_batch_device(dev, d_base, _p64(offs), _p64(lens), n,
+                                            _device_buffer("sha256 digests", sha, 32 * n, dev, align=16),
+                                            _device_buffer("md5 digests", m5, 16 * n, dev, align=16),
                                             _stream_handle(stream)))
     return sha, m5
 
@@ -334,13 +374,14 @@ def verify_batch_device(data, offsets, lengths, expected, algo: str = "sha256", 
     import torch
     a = _native.ALGO_IDS[algo]
     offs, lens = _u64(offsets), _u64(lengths)
+    d_base = _device_buffer("data", data, _extent(offs, lens))
+    dev = data.device.index
+    d_exp = _device_buffer("expected", expected, 4 * _native.DIGEST_WORDS[a] * offs.size, dev, align=4)
     mism = torch.zeros(offs.size, dtype=torch.uint8, device=data.device)
     cnt = ctypes.c_uint64(0)
-    check(lib().s3h_verify_batch_device(data.device.index, a, ctypes.c_void_p(data.data_ptr()),
-                                        _p64(offs), _p64(lens), offs.size,
-                                        ctypes.c_void_p(expected.data_ptr()),
-                                        ctypes.c_void_p(mism.data_ptr()), ctypes.byref(cnt),
-                                        ctypes.c_void_p(_stream_handle(stream))))
+    check(lib().s3h_verify_batch_device(dev, a, d_base, _p64(offs), _p64(lens), offs.size, d_exp,
+                                        _device_buffer("mask", mism, offs.size, dev),
+                                        ctypes.byref(cnt), ctypes.c_void_p(_stream_handle(stream))))
     return cnt.value, mism.bool()
 
 
@@ -380,19 +421,15 @@ class CrcPlan:
                                                     ctypes.byref(sb), ctypes.byref(g)))
         return {"n": n.value, "segments": segs.value, "segment_bytes": sb.value, "grid": g.value}
 
+    def _crcs_ptr(self, crcs) -> ctypes.c_void_p:
+        return _device_buffer("crcs", crcs, self._value_bytes * self.n, self.device,
+                              align=self._value_bytes)
+
     def launch(self, data, crcs, stream=None) -> None:
         """CRC of every part of ``data`` (device tensor) into ``crcs`` (n 32-bit words, device).
         Asynchronous on ``stream``."""
-        if not (data.is_cuda and crcs.is_cuda):
-            raise ValueError("data and crcs must be device tensors")
-        if crcs.numel() * crcs.element_size() < self._value_bytes * self.n:
-            raise ValueError(f"crcs buffer too small (need n*{self._value_bytes} bytes)")
-        end = int((self.offsets + self.lengths).max()) if self.n else 0
-        if data.numel() * data.element_size() < end:
-            raise ValueError(f"data buffer ({data.numel() * data.element_size()} B) smaller "
-                             f"than the plan's extent ({end} B)")
-        check(getattr(lib(), self._prefix + "launch")(self._h, ctypes.c_void_p(data.data_ptr()),
-                                                      ctypes.c_void_p(crcs.data_ptr()),
+        d_base = _device_buffer("data", data, _extent(self.offsets, self.lengths), self.device)
+        check(getattr(lib(), self._prefix + "launch")(self._h, d_base, self._crcs_ptr(crcs),
                                                       ctypes.c_void_p(_stream_handle(stream))))
 
     def launch_range(self, data, crcs, byte_begin: int, byte_end: int, byte_origin: int = 0,
@@ -402,20 +439,15 @@ class CrcPlan:
         stay in the plan.  ``crcs[p]`` is written by the launch whose range holds part p's last
         byte (an empty part's by a launch with byte_begin == 0), no other entry is touched.
         byte_begin is 0 (a new pass) or the previous ranged launch's byte_end."""
-        if not (data.is_cuda and crcs.is_cuda):
-            raise ValueError("data and crcs must be device tensors")
-        if crcs.numel() * crcs.element_size() < self._value_bytes * self.n:
-            raise ValueError(f"crcs buffer too small (need n*{self._value_bytes} bytes)")
+        end = 0
         if byte_origin <= byte_begin < byte_end and self.n:  # (the library rejects the rest)
             top = np.minimum(self.lengths, np.uint64(byte_end))
             live = top > np.uint64(byte_begin)
             end = int((self.offsets[live] + top[live]).max()) - byte_origin if live.any() else 0
-            if data.numel() * data.element_size() < end:
-                raise ValueError(f"data buffer ({data.numel() * data.element_size()} B) smaller "
-                                 f"than the range's extent ({end} B)")
+        d_base = _device_buffer("data", data, end, self.device)
         check(getattr(lib(), self._prefix + "launch_range")(
-            self._h, ctypes.c_void_p(data.data_ptr()), ctypes.c_void_p(crcs.data_ptr()), byte_begin,
-            byte_end, byte_origin, ctypes.c_void_p(_stream_handle(stream))))
+            self._h, d_base, self._crcs_ptr(crcs), byte_begin, byte_end, byte_origin,
+            ctypes.c_void_p(_stream_handle(stream))))
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -441,13 +473,11 @@ def crc_batch_device(data, offsets, lengths, algo: str | int = "crc32c", stream=
     (``.cpu().numpy().view(np.uint32)``), what zlib.crc32 returns for CRC-32.  Blocking."""
     import torch
     offs, lens = _u64(offsets), _u64(lengths)
-    end = int((offs + lens).max()) if offs.size else 0
-    if not data.is_cuda or data.numel() * data.element_size() < end:
-        raise ValueError("data must be a device tensor that covers every part")
+    d_base = _device_buffer("data", data, _extent(offs, lens))
+    dev = data.device.index
     out = torch.empty(offs.size, dtype=torch.int32, device=data.device)
-    check(lib().s3h_crc_batch_device(data.device.index, _crc_id(algo),
-                                     ctypes.c_void_p(data.data_ptr()), _p64(offs), _p64(lens),
-                                     offs.size, ctypes.c_void_p(out.data_ptr()),
+    check(lib().s3h_crc_batch_device(dev, _crc_id(algo), d_base, _p64(offs), _p64(lens),
+                                     offs.size, _device_buffer("crcs", out, 4 * offs.size, dev, align=4),
                                      ctypes.c_void_p(_stream_handle(stream))))
     return out
 
@@ -498,13 +528,15 @@ def crc_verify_batch_device(data, offsets, lengths, expected, algo: str | int = 
     (mismatch count, bool mask on the device)."""
     import torch
     offs, lens = _u64(offsets), _u64(lengths)
+    d_base = _device_buffer("data", data, _extent(offs, lens))
+    dev = data.device.index
+    d_exp = _device_buffer("expected", expected, 4 * offs.size, dev, align=4)
     mism = torch.zeros(offs.size, dtype=torch.uint8, device=data.device)
     cnt = ctypes.c_uint64(0)
-    check(lib().s3h_crc_verify_batch_device(data.device.index, _crc_id(algo),
-                                            ctypes.c_void_p(data.data_ptr()), _p64(offs),
-                                            _p64(lens), offs.size,
-                                            ctypes.c_void_p(expected.data_ptr()),
-                                            ctypes.c_void_p(mism.data_ptr()), ctypes.byref(cnt),
+    check(lib().s3h_crc_verify_batch_device(dev, _crc_id(algo), d_base, _p64(offs), _p64(lens),
+                                            offs.size, d_exp,
+                                            _device_buffer("mask", mism, offs.size, dev),
+                                            ctypes.byref(cnt),
                                             ctypes.c_void_p(_stream_handle(stream))))
     return cnt.value, mism.bool()
 
@@ -748,33 +780,26 @@ class ChunkSignPlan:
         return {"n": n.value, "data_chunks": c.value, "signatures": s.value,
                 "max_chunks_per_part": m.value, "kernel": name.value.decode()}
 
+    def _ptrs(self, *args) -> list:
+        # (name, tensor or raw device pointer, bytes needed, alignment) -> validated pointers
+        return [_device_buffer(name, t, need, self.device, align, raw=True)
+                for name, t, need, align in args]
+
     def launch(self, data, ctx: ChunkSignContext, seeds, out, stream=None) -> None:
         """Hash every chunk of ``data`` and chain the signatures into ``out`` (signatures x 8
         words) from ``seeds`` (n x 8 words).  Device tensors, or raw device pointers (ints)."""
-        ptrs = []
-        for t, need in ((data, int((self.offsets + self.lengths).max()) if self.n else 0),
-                        (seeds, 32 * self.n), (out, 32 * self.signatures)):
-            if isinstance(t, int):
-                ptrs.append(t)
-                continue
-            if not t.is_cuda:
-                raise ValueError("data, seeds and out must be device tensors")
-            if t.numel() * t.element_size() < need:
-                raise ValueError(f"buffer of {t.numel() * t.element_size()} B, need {need} B")
-            ptrs.append(t.data_ptr())
-        check(lib().s3h_chunk_plan_launch(self._h, ctx._h, ctypes.c_void_p(ptrs[0]),
-                                          ctypes.c_void_p(ptrs[1]), ctypes.c_void_p(ptrs[2]),
+        ptrs = self._ptrs(("data", data, _extent(self.offsets, self.lengths), 1),
+                          ("seeds", seeds, 32 * self.n, 16), ("out", out, 32 * self.signatures, 16))
+        check(lib().s3h_chunk_plan_launch(self._h, ctx._h, *ptrs,
                                           ctypes.c_void_p(_stream_handle(stream))))
 
     def chain(self, ctx: ChunkSignContext, chunk_digests, seeds, out, stream=None) -> None:
         """The chain kernel alone over ``chunk_digests`` (device tensor, data chunks x 8 words in
         this plan's geometry) that the caller hashed itself (s3h_chunk_plan_chain)."""
         chunks = int(self.data_chunks_per_part.sum())
-        for t, need in ((chunk_digests, 32 * chunks), (seeds, 32 * self.n), (out, 32 * self.signatures)):
-            if not t.is_cuda or t.numel() * t.element_size() < need:
-                raise ValueError(f"need a device tensor of at least {need} B")
-        check(lib().s3h_chunk_plan_chain(self._h, ctx._h, ctypes.c_void_p(chunk_digests.data_ptr()),
-                                         ctypes.c_void_p(seeds.data_ptr()), ctypes.c_void_p(out.data_ptr()),
+        ptrs = self._ptrs(("chunk_digests", chunk_digests, 32 * chunks, 16),
+                          ("seeds", seeds, 32 * self.n, 16), ("out", out, 32 * self.signatures, 16))
+        check(lib().s3h_chunk_plan_chain(self._h, ctx._h, *ptrs,
                                          ctypes.c_void_p(_stream_handle(stream))))
 
     def _value_bytes(self) -> int:
@@ -787,31 +812,22 @@ class ChunkSignPlan:
         """``launch``, then each part's CRC into ``checksums`` (n 32-bit words, or 64-bit for
         crc64nvme) and its trailer signature into ``trailer_out`` (n x 8 words), all on
         ``stream`` (s3h_chunk_plan_launch_trailer).  Device tensors, or raw device pointers."""
-        ptrs = []
-        for t, need in ((data, int((self.offsets + self.lengths).max()) if self.n else 0),
-                        (seeds, 32 * self.n), (out, 32 * self.signatures),
-                        (checksums, self._value_bytes() * self.n), (trailer_out, 32 * self.n)):
-            if isinstance(t, int):
-                ptrs.append(t)
-                continue
-            if not t.is_cuda:
-                raise ValueError("data, seeds and the outputs must be device tensors")
-            if t.numel() * t.element_size() < need:
-                raise ValueError(f"buffer of {t.numel() * t.element_size()} B, need {need} B")
-            ptrs.append(t.data_ptr())
-        check(lib().s3h_chunk_plan_launch_trailer(self._h, ctx._h, *(ctypes.c_void_p(p) for p in ptrs),
+        vb = self._value_bytes()
+        ptrs = self._ptrs(("data", data, _extent(self.offsets, self.lengths), 1),
+                          ("seeds", seeds, 32 * self.n, 16), ("out", out, 32 * self.signatures, 16),
+                          ("checksums", checksums, vb * self.n, vb),
+                          ("trailer_out", trailer_out, 32 * self.n, 16))
+        check(lib().s3h_chunk_plan_launch_trailer(self._h, ctx._h, *ptrs,
                                                   ctypes.c_void_p(_stream_handle(stream))))
 
     def trailer(self, ctx: ChunkSignContext, signatures, checksums, trailer_out, stream=None) -> None:
         """The trailer kernel alone over chunk ``signatures`` (this plan's geometry) and
         ``checksums`` already on the device (s3h_chunk_plan_trailer)."""
-        for t, need in ((signatures, 32 * self.signatures), (checksums, self._value_bytes() * self.n),
-                        (trailer_out, 32 * self.n)):
-            if not t.is_cuda or t.numel() * t.element_size() < need:
-                raise ValueError(f"need a device tensor of at least {need} B")
-        check(lib().s3h_chunk_plan_trailer(self._h, ctx._h, ctypes.c_void_p(signatures.data_ptr()),
-                                           ctypes.c_void_p(checksums.data_ptr()),
-                                           ctypes.c_void_p(trailer_out.data_ptr()),
+        vb = self._value_bytes()
+        ptrs = self._ptrs(("signatures", signatures, 32 * self.signatures, 16),
+                          ("checksums", checksums, vb * self.n, vb),
+                          ("trailer_out", trailer_out, 32 * self.n, 16))
+        check(lib().s3h_chunk_plan_trailer(self._h, ctx._h, *ptrs,
                                            ctypes.c_void_p(_stream_handle(stream))))
 
     def status(self, stream=None) -> None:
@@ -845,8 +861,8 @@ def chunk_sign_batch_device(data, offsets, lengths, chunk_bytes: int, ctx: Chunk
     n = int(lens.size)
     sd = _words(seeds, n, "seeds")
     out = np.zeros((chunk_geometry(lens, chunk_bytes)["signatures"], 8), dtype=np.uint32)
-    check(lib().s3h_chunk_sign_batch_device(data.device.index or 0, ctx._h,
-                                            ctypes.c_void_p(data.data_ptr()), _p64(offs), _p64(lens),
+    d_base = _device_buffer("data", data, _extent(offs, lens))
+    check(lib().s3h_chunk_sign_batch_device(data.device.index or 0, ctx._h, d_base, _p64(offs), _p64(lens),
                                             n, int(chunk_bytes), sd.ctypes.data, out.ctypes.data))
     return out
 
@@ -932,8 +948,9 @@ def chunk_sign_trailer_batch_device(data, offsets, lengths, chunk_bytes: int, ct
     n = int(lens.size)
     sd = _words(seeds, n, "seeds")
     sigs, vals, tsig = _trailer_outputs(trailer, lens, chunk_bytes)
+    d_base = _device_buffer("data", data, _extent(offs, lens))
     check(lib().s3h_chunk_sign_trailer_batch_device(data.device.index or 0, ctx._h, _trailer_id(trailer),
-                                                    ctypes.c_void_p(data.data_ptr()), _p64(offs),
+                                                    d_base, _p64(offs),
                                                     _p64(lens), n, int(chunk_bytes), sd.ctypes.data,
                                                     sigs.ctypes.data, vals.ctypes.data, tsig.ctypes.data))
     return sigs, vals, tsig
@@ -984,13 +1001,11 @@ def crc64_batch_device(data, offsets, lengths, stream=None):
     (``.cpu().numpy().view(np.uint64)``).  Blocking."""
     import torch
     offs, lens = _u64(offsets), _u64(lengths)
-    end = int((offs + lens).max()) if offs.size else 0
-    if not data.is_cuda or data.numel() * data.element_size() < end:
-        raise ValueError("data must be a device tensor that covers every part")
+    d_base = _device_buffer("data", data, _extent(offs, lens))
+    dev = data.device.index
     out = torch.empty(offs.size, dtype=torch.int64, device=data.device)
-    check(lib().s3h_crc64nvme_batch_device(data.device.index, ctypes.c_void_p(data.data_ptr()),
-                                           _p64(offs), _p64(lens), offs.size,
-                                           ctypes.c_void_p(out.data_ptr()),
+    check(lib().s3h_crc64nvme_batch_device(dev, d_base, _p64(offs), _p64(lens), offs.size,
+                                           _device_buffer("crcs", out, 8 * offs.size, dev, align=8),
                                            ctypes.c_void_p(_stream_handle(stream))))
     return out
 
@@ -1000,15 +1015,14 @@ def crc64_verify_batch_device(data, offsets, lengths, expected, stream=None):
     (mismatch count, bool mask on the device)."""
     import torch
     offs, lens = _u64(offsets), _u64(lengths)
-    if expected.numel() * expected.element_size() < 8 * offs.size:
-        raise ValueError("expected buffer too small (need n*8 bytes)")
+    d_base = _device_buffer("data", data, _extent(offs, lens))
+    dev = data.device.index
+    d_exp = _device_buffer("expected", expected, 8 * offs.size, dev, align=4)
     mism = torch.zeros(offs.size, dtype=torch.uint8, device=data.device)
     cnt = ctypes.c_uint64(0)
-    check(lib().s3h_crc64nvme_verify_batch_device(data.device.index,
-                                                  ctypes.c_void_p(data.data_ptr()), _p64(offs),
-                                                  _p64(lens), offs.size,
-                                                  ctypes.c_void_p(expected.data_ptr()),
-                                                  ctypes.c_void_p(mism.data_ptr()),
+    check(lib().s3h_crc64nvme_verify_batch_device(dev, d_base, _p64(offs), _p64(lens), offs.size,
+                                                  d_exp,
+                                                  _device_buffer("mask", mism, offs.size, dev),
                                                   ctypes.byref(cnt),
                                                   ctypes.c_void_p(_stream_handle(stream))))
     return cnt.value, mism.bool()
@@ -1130,9 +1144,8 @@ class Stream:
         offs, lens = _u64(offsets), _u64(lengths)
         if offs.size != self.n or lens.size != self.n:
             raise ValueError(f"need one chunk per message ({self.n})")
-        if lens.any() and int((offs + lens)[lens > 0].max()) > data.numel() * data.element_size():
-            raise ValueError("chunk extends past the data tensor")
-        check(lib().s3h_stream_update_device(self._h, ctypes.c_void_p(data.data_ptr()),
+        end = int((offs + lens)[lens > 0].max()) if lens.any() else 0
+        check(lib().s3h_stream_update_device(self._h, _device_buffer("data", data, end, self.device),
                                              _p64(offs), _p64(lens),
                                              ctypes.c_void_p(_stream_handle(stream))))
 
@@ -1143,9 +1156,9 @@ class Stream:
         return out
 
     def final_device(self, digests, stream=None) -> None:
-        if digests.numel() * digests.element_size() < 4 * self.words * self.n:
-            raise ValueError("digests buffer too small")
-        check(lib().s3h_stream_final_device(self._h, ctypes.c_void_p(digests.data_ptr()),
+        d_dig = _device_buffer("digests", digests, 4 * self.words * self.n, self.device,
+                               align=_digest_align(self.algo))
+        check(lib().s3h_stream_final_device(self._h, d_dig,
                                             ctypes.c_void_p(_stream_handle(stream))))
 
     def status(self, stream=None) -> None:
@@ -1545,10 +1558,11 @@ def trim() -> None:
 def generate_parts(data, offsets, lengths, part_ids, seed: int, stream=None) -> None:
     """Fill parts of device tensor ``data`` with generator G(seed, part_id, length)."""
     offs, lens, ids = _u64(offsets), _u64(lengths), _u64(part_ids)
+    d_base = _device_buffer("data", data, _extent(offs, lens), align=8)
     dev = data.device.index
     for s in range(0, offs.size, 65535):
         e = min(offs.size, s + 65535)
-        check(lib().s3h_generate_parts(dev, ctypes.c_void_p(data.data_ptr()), _p64(offs[s:e]),
+        check(lib().s3h_generate_parts(dev, d_base, _p64(offs[s:e]),
                                        _p64(lens[s:e]), _p64(ids[s:e]), e - s, seed,
                                        ctypes.c_void_p(_stream_handle(stream))))
 

@@ -69,6 +69,11 @@ int main() {
     mismatch = true;
   }
   CHECK(mismatch);
+  // 64-bit values are 8-byte aligned: a pointer 4 bytes off is refused before any device is
+  // looked for, through the wrappers' error path (the pointers are never dereferenced)
+  alignas(16) static uint8_t fake[32];
+  CHECK(throws_einval([&] { crc64::crc_batch_device(0, fake, {0}, {9}, reinterpret_cast<uint64_t*>(fake + 20)); }));
+  CHECK(std::strstr(s3h_last_error(), "8-byte aligned"));
   std::puts("ok");
   return 0;
 }

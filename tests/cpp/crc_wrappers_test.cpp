@@ -31,6 +31,16 @@ int main() {
     threw = e.code == S3H_EINVAL;
   }
   CHECK(threw);
+  // a CRC pointer that is not 4-byte aligned is refused before any device is looked for, and
+  // reported through the wrappers' error path (the pointers are never dereferenced)
+  alignas(16) static uint8_t fake[32];
+  threw = false;
+  try {
+    crc::crc_batch_device(0, S3H_CRC32C, fake, {0}, {9}, reinterpret_cast<uint32_t*>(fake + 18));
+  } catch (const sha256::batch_error& e) {
+    threw = e.code == S3H_EINVAL && std::strstr(e.what(), "aligned");
+  }
+  CHECK(threw);
   std::puts("ok");
   return 0;
 }

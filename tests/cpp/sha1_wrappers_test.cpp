@@ -112,6 +112,13 @@ int main(int argc, char** argv) {
   CHECK(s3h_plan_create_ex(0, S3H_ALGO_SHA1, zero, zero, 1, S3H_KERNEL_SKEW, &plan) == S3H_EINVAL);
   CHECK(std::strstr(s3h_last_error(), "SHA-1"));
   CHECK(plan == nullptr);
+  // digest pointers: SHA-1 takes any 4-byte aligned one, SHA-256 needs 16; a pointer that misses
+  // it is refused before any device is looked for (the pointers are never dereferenced)
+  alignas(16) static uint8_t fake[64];
+  CHECK(throws_einval([&] { sha1::sha1_batch_device(0, fake, {0}, {3}, reinterpret_cast<uint32_t*>(fake + 18)); }));
+  CHECK(std::strstr(s3h_last_error(), "4-byte aligned"));
+  CHECK(throws_einval([&] { sha256::sha256_batch_device(0, fake, {0}, {3}, reinterpret_cast<uint32_t*>(fake + 20)); }));
+  CHECK(std::strstr(s3h_last_error(), "16-byte aligned"));
 
   // empty batches are no call at all; size mismatches never reach the library
   CHECK(sha1::sha1_batch({}, {}).empty());
