@@ -22,7 +22,7 @@ LIB := $(LIBDIR)/libs3hash.so
 all: $(LIB) oracle cpptests
 
 # libs3hash.so = one device unit (launch.hip: the kernels of sha256_kernels.hip, sha1_kernels.hip,
-# crc32_kernels.hip / crc64_kernels.hip, chunk_sign_kernels.hip and chunk_trailer_kernels.hip and their launches) + host units by concern (internal.hpp lists them) + the CPU drop-in.
+# crc32_kernels.hip / crc64_kernels.hip, chunk_sign_kernels.hip, chunk_trailer_kernels.hip and chunk_body_kernels.hip and their launches) + host units by concern (internal.hpp lists them) + the CPU drop-in.
 HOST_UNITS := status topology plan pinned host_path stream route_plan route crc chunk_sign
 HOST_OBJS := $(HOST_UNITS:%=$(OBJDIR)/%.o)
 CPU_OBJS := $(OBJDIR)/lib_hash.o $(OBJDIR)/lib_md5.o $(OBJDIR)/lib_crc.o $(OBJDIR)/lib_crc64.o $(OBJDIR)/lib_sha1.o $(OBJDIR)/lib_chunk_sign.o
@@ -34,7 +34,7 @@ KERNEL_OBJ := $(OBJDIR)/launch.o
 ISA_DIS := build/isa/libs3hash_gfx950.dis
 # (explicit prerequisites: the -MMD file is written from build/isa, so its relative paths do not
 # resolve from the repo root)
-KERNEL_SRCS := $(CSRC)/launch.hip $(CSRC)/sha256_kernels.hip $(CSRC)/sha1_kernels.hip $(CSRC)/crc32_kernels.hip $(CSRC)/crc64_kernels.hip $(CSRC)/chunk_sign_kernels.hip $(CSRC)/chunk_trailer_kernels.hip $(wildcard $(CSRC)/*.inc) \
+KERNEL_SRCS := $(CSRC)/launch.hip $(CSRC)/sha256_kernels.hip $(CSRC)/sha1_kernels.hip $(CSRC)/crc32_kernels.hip $(CSRC)/crc64_kernels.hip $(CSRC)/chunk_sign_kernels.hip $(CSRC)/chunk_trailer_kernels.hip $(CSRC)/chunk_body_kernels.hip $(wildcard $(CSRC)/*.inc) \
                $(CSRC)/crc_math.hpp $(CSRC)/crc64_math.hpp $(CSRC)/sha256_device.hpp $(CSRC)/kernel_abi.hpp $(CSRC)/exp_config.hpp $(CSRC)/internal.hpp
 $(KERNEL_OBJ): $(KERNEL_SRCS)
 	@mkdir -p $(OBJDIR) build/isa
@@ -69,7 +69,7 @@ oracle: $(LIB)
 	$(MAKE) -C oracle
 
 CPPTESTS := tests/cpp/build/dropin_test tests/cpp/build/sign_test tests/cpp/build/chunk_sign_wrappers_test \
-            tests/cpp/build/chunk_trailer_wrappers_test
+            tests/cpp/build/chunk_trailer_wrappers_test tests/cpp/build/chunk_body_wrappers_test
 cpptests: $(CPPTESTS) apps/build/s3-upload-hash
 
 apps/build/s3-upload-hash: apps/s3_upload_hash.cpp s3client_amd/host/aws_sign.cpp s3client_amd/host/aws_sign.h include/s3hash_batch.hpp $(LIB)
@@ -86,6 +86,10 @@ tests/cpp/build/chunk_sign_wrappers_test: tests/cpp/chunk_sign_wrappers_test.cpp
 	$(CXX) -O1 -std=c++17 -Wall -Wextra -Werror -Iinclude -o $@ $< -L$(LIBDIR) -ls3hash -Wl,-rpath,'$$ORIGIN/../../../$(LIBDIR)'
 
 tests/cpp/build/chunk_trailer_wrappers_test: tests/cpp/chunk_trailer_wrappers_test.cpp include/s3hash_batch.hpp $(LIB)
+	@mkdir -p tests/cpp/build
+	$(CXX) -O1 -std=c++17 -Wall -Wextra -Werror -Iinclude -o $@ $< -L$(LIBDIR) -ls3hash -Wl,-rpath,'$$ORIGIN/../../../$(LIBDIR)'
+
+tests/cpp/build/chunk_body_wrappers_test: tests/cpp/chunk_body_wrappers_test.cpp include/s3hash_batch.hpp $(LIB)
 	@mkdir -p tests/cpp/build
 	$(CXX) -O1 -std=c++17 -Wall -Wextra -Werror -Iinclude -o $@ $< -L$(LIBDIR) -ls3hash -Wl,-rpath,'$$ORIGIN/../../../$(LIBDIR)'
 

@@ -26,6 +26,9 @@
  *   s3h_chunk_plan_create_trailer / _launch_trailer / _trailer, s3h_chunk_sign_trailer_batch_*,
  *       s3h_cpu_trailer_signatures, s3h_chunk_trailer_text  -- the same bodies closed by a trailing
  *       checksum header and its signature (STREAMING-AWS4-HMAC-SHA256-PAYLOAD-TRAILER).
+ *   s3h_chunk_body_geometry, s3h_cpu_chunk_body, s3h_chunk_plan_body / _body_info,
+ *       s3h_chunk_body_batch_device  -- those bodies themselves: the framed bytes an uploader
+ *       sends and their lengths (Content-Length), on the device or the CPU.
  *
  * Digest layout (every entry point): 8 uint32 words per part with word i = bswap32(H_i),
  * exactly lib/hash's `to_little` output (sha256.h:103-106); on little-endian hosts the 32
@@ -54,7 +57,9 @@ extern "C" {
  * s3h_chunk_header_text, s3h_chunk_geometry, s3h_chunk_plan_*, s3h_chunk_sign_batch_device / _host),
  * then their trailer signatures (s3h_cpu_trailer_signatures, s3h_trailer_line_text,
  * s3h_chunk_trailer_text, s3h_chunk_plan_create_trailer, s3h_chunk_plan_launch_trailer,
- * s3h_chunk_plan_trailer, s3h_chunk_plan_trailer_info, s3h_chunk_sign_trailer_batch_device / _host). */
+ * s3h_chunk_plan_trailer, s3h_chunk_plan_trailer_info, s3h_chunk_sign_trailer_batch_device / _host),
+ * then the bodies (s3h_chunk_body_geometry, s3h_cpu_chunk_body, s3h_chunk_plan_body,
+ * s3h_chunk_plan_body_info, s3h_chunk_body_batch_device). */
 #define S3H_API_VERSION 2
 
 enum s3h_status {
@@ -851,8 +856,9 @@ int s3h_chunk_sign_batch_host(s3h_chunk_sign_ctx_t ctx, const uint8_t *const *pa
  * fills the GPU.  The digest checksums are accepted by the CPU functions and the host-resident
  * entry point only: a part's SHA-1 or SHA-256 is a whole-part chain, which is what chunk signing
  * exists to avoid, so the device entry points return S3H_EINVAL for them.
- * The framing s3h_chunk_trailer_text writes follows the AWS documentation; it has not been
- * pinned against a real server (the tests' mock endpoint does not decode aws-chunked bodies).
+ * The framing s3h_chunk_trailer_text writes follows the AWS documentation; the tests pin it, as
+ * part of whole bodies, against an independent decoder (the section after this one), but no real
+ * server has seen it (the tests' mock endpoint does not decode aws-chunked bodies).
  * Added within API version 2. */
 enum s3h_trailer_checksum {
   S3H_TRAILER_CRC32C = 0,
@@ -919,6 +925,63 @@ int s3h_chunk_sign_trailer_batch_host(s3h_chunk_sign_ctx_t ctx, int checksum,
                                       uint64_t n, uint64_t chunk_bytes, const uint32_t *seeds,
                                       uint32_t *signatures, void *checksums,
                                       uint32_t *trailer_signatures);
+
+/* ---------------------------------------------------------------- aws-chunked bodies
+ * The bytes an uploader sends for a chunk-signed part, from the signatures of the two sections
+ * above.  For a part of L bytes at chunk_bytes c: floor(L / c) chunks of c bytes and one of
+ * L mod c bytes if that is not zero, each framed as s3h_chunk_header_text frames it,
+ *   hex(k) ";chunk-signature=" <64 hex> "\r\n" <k bytes> "\r\n"        hexlen(k) + 85 + k bytes
+ * then the line of the final chunk, "0;chunk-signature=" <64 hex> "\r\n" (84 bytes), then "\r\n",
+ * or with a trailing checksum the text of s3h_chunk_trailer_text (name ":" base64 + 94 bytes).
+ * Chunk i of part p carries signature row signature_offsets[p] + i (s3h_chunk_geometry), the
+ * final line the part's last row.  The body's length is the request's Content-Length, the
+ * part's own length its x-amz-decoded-content-length.  The AWS documentation's example (66,560
+ * bytes at 65,536-byte chunks) gives 66,824 bytes, 66,946 with a CRC-32C trailer.
+ * Added within API version 2. */
+/* Pure host arithmetic, no device.  checksum: -1 (no trailer) or any enum s3h_trailer_checksum.
+ * body_lengths[p]: the wire length of part p's body; body_offsets[p]: where it starts when the
+ * bodies are packed back to back; *total: their sum.  Any output may be null.  Errors as
+ * s3h_chunk_geometry, and S3H_EINVAL for an unknown checksum. */
+int s3h_chunk_body_geometry(const uint64_t *lengths, uint64_t n, uint64_t chunk_bytes,
+                            int checksum, uint64_t *body_lengths, uint64_t *body_offsets,
+                            uint64_t *total);
+/* Host-resident parts: part p's body at body + body_offsets[p] (null: packed, as
+ * s3h_chunk_body_geometry packs them), exactly its bytes and nothing else.  signatures as
+ * s3h_cpu_chunk_signatures returns them.  checksum -1: values and trailer_signatures null; any
+ * enum s3h_trailer_checksum: values (n entries in the kind's layout) and trailer_signatures
+ * (n x 8 words), both needed.  parts[p] may be null for an empty part.  Parts are spread over
+ * the host threads. */
+int s3h_cpu_chunk_body(const uint8_t *const *parts, const uint64_t *lengths, uint64_t n,
+                       uint64_t chunk_bytes, const uint32_t *signatures, int checksum,
+                       const void *values, const uint32_t *trailer_signatures, uint8_t *body,
+                       const uint64_t *body_offsets);
+/* Device-resident parts of a chunk plan, asynchronous on `stream`: part p's body at
+ * d_body + body_offsets[p] (a host array of n byte offsets, any values, reusable on return;
+ * null: packed).  d_body needs no alignment.  d_signatures as s3h_chunk_plan_launch wrote them;
+ * a trailer plan writes the trailer form and needs d_checksums and d_trailer_signatures as
+ * s3h_chunk_plan_launch_trailer wrote them, a plain plan needs both null.  Queued behind those
+ * launches on the same stream it needs no host synchronisation in between.  The kernel reads the
+ * parts and the three inputs and writes every byte of every body once, nothing else.
+ * S3H_EINVAL, with nothing started: two bodies overlap, the bodies' extent intersects the
+ * parts' (d_base + their offsets), a pointer is null where one is needed or given where none is,
+ * d_signatures is not 4-byte aligned or d_checksums not aligned to its values. */
+int s3h_chunk_plan_body(s3h_chunk_plan_t plan, const void *d_base, const uint32_t *d_signatures,
+                        const void *d_checksums, const uint32_t *d_trailer_signatures,
+                        void *d_body, const uint64_t *body_offsets, void *stream);
+/* The plan's body lengths (n entries) and their sum, and the body kernel's shape: its work items
+ * (one wave each: the pieces of the data chunks and one per part), the most bytes of one chunk
+ * that one item copies, and its grid (workgroups).  Any output may be null. */
+int s3h_chunk_plan_body_info(s3h_chunk_plan_t plan, uint64_t *body_lengths, uint64_t *total,
+                             uint64_t *items, uint64_t *piece_bytes, uint64_t *grid);
+/* One-shot, blocking: plan + launch (checksum -1) or trailer launch (a CRC kind) + body + status
+ * + copy back.  body_host receives part p's body at body_offsets[p] (null: packed; the packed
+ * bodies come back in one copy).  S3H_ENOMEM when the device buffer for the bodies cannot be
+ * allocated. */
+int s3h_chunk_body_batch_device(int device, s3h_chunk_sign_ctx_t ctx, int checksum,
+                                const void *d_base, const uint64_t *offsets,
+                                const uint64_t *lengths, uint64_t n, uint64_t chunk_bytes,
+                                const uint32_t *seeds_host, uint8_t *body_host,
+                                const uint64_t *body_offsets);
 
 /* ---------------------------------------------------------------- synthetic inputs
  * Fill part i (at d_base + offsets[i], 8-B aligned, lengths[i] bytes) with generator

@@ -624,6 +624,18 @@ class ChunkSignPlan {
              uint32_t* d_signatures, void* stream = nullptr) {
     sha256::batch_check(s3h_chunk_plan_chain(p_, ctx.get(), d_chunk_digests, d_seeds, d_signatures, stream));
   }
+  // Asynchronous, behind launch() on the same stream: part p's aws-chunked body at
+  // d_body + body_offsets[p] (host array; null: packed back to back) (s3h_chunk_plan_body).
+  void body(const void* d_base, const uint32_t* d_signatures, void* d_body, const uint64_t* body_offsets = nullptr,
+            void* stream = nullptr) {
+    sha256::batch_check(s3h_chunk_plan_body(p_, d_base, d_signatures, nullptr, nullptr, d_body, body_offsets, stream));
+  }
+  // The plan's body lengths (Content-Length of each part's request) and their sum.
+  std::vector<uint64_t> body_lengths(uint64_t* total = nullptr) const {
+    std::vector<uint64_t> out(signature_offsets_.size());
+    sha256::batch_check(s3h_chunk_plan_body_info(p_, out.data(), total, nullptr, nullptr, nullptr));
+    return out;
+  }
   void status(void* stream = nullptr) { sha256::batch_check(s3h_chunk_plan_status(p_, stream)); }
   uint64_t signatures() const { return signatures_; }
   // Row of part p's first signature.
@@ -733,6 +745,20 @@ class ChunkTrailerPlan {
     sha256::batch_check(s3h_chunk_plan_trailer(p_, ctx.get(), d_signatures, d_checksums, d_trailer_signatures,
                                                stream));
   }
+  // Asynchronous, behind launch() on the same stream: part p's body in the trailer form at
+  // d_body + body_offsets[p] (host array; null: packed back to back) (s3h_chunk_plan_body).
+  void body(const void* d_base, const uint32_t* d_signatures, const void* d_checksums,
+            const uint32_t* d_trailer_signatures, void* d_body, const uint64_t* body_offsets = nullptr,
+            void* stream = nullptr) {
+    sha256::batch_check(s3h_chunk_plan_body(p_, d_base, d_signatures, d_checksums, d_trailer_signatures, d_body,
+                                            body_offsets, stream));
+  }
+  // The plan's body lengths (Content-Length of each part's request) and their sum.
+  std::vector<uint64_t> body_lengths(uint64_t* total = nullptr) const {
+    std::vector<uint64_t> out(signature_offsets_.size());
+    sha256::batch_check(s3h_chunk_plan_body_info(p_, out.data(), total, nullptr, nullptr, nullptr));
+    return out;
+  }
   void status(void* stream = nullptr) { sha256::batch_check(s3h_chunk_plan_status(p_, stream)); }
   int checksum() const { return checksum_; }
   uint64_t signatures() const { return signatures_; }
@@ -774,6 +800,62 @@ inline ChunkTrailerResult chunk_trailer_signatures_host(const ChunkSignContext& 
                        : checksum == S3H_TRAILER_SHA256 ? 32 : 4;
   r.checksums.resize(per * parts.size());
   return r;
+}
+
+// ---- the bodies themselves: the framed bytes of a chunk-signed part.  `checksum` is -1 (no
+// trailer) or an s3h_trailer_checksum.
+
+// Wire length of each part's body (its request's Content-Length), where each starts when they are
+// packed back to back, and their sum (s3h_chunk_body_geometry; no device).
+struct ChunkBodyGeometry {
+  std::vector<uint64_t> lengths, offsets;
+  uint64_t total = 0;
+};
+inline ChunkBodyGeometry chunk_body_geometry(const std::vector<uint64_t>& lengths, uint64_t chunk_bytes,
+                                             int checksum = -1) {
+  ChunkBodyGeometry g;
+  g.lengths.resize(lengths.size());
+  g.offsets.resize(lengths.size());
+  sha256::batch_check(s3h_chunk_body_geometry(lengths.data(), lengths.size(), chunk_bytes, checksum,
+                                              g.lengths.data(), g.offsets.data(), &g.total));
+  return g;
+}
+
+// Host-resident parts -> their bodies packed back to back (s3h_cpu_chunk_body).  `signatures` as
+// ChunkSignContext::signatures returns them; with a checksum, `values` (one per part in the kind's
+// layout) and `trailer_signatures` (8 words per part).
+inline std::vector<uint8_t> chunk_body_host(const std::vector<const uint8_t*>& parts,
+                                            const std::vector<uint64_t>& lengths, uint64_t chunk_bytes,
+                                            const std::vector<uint32_t>& signatures, int checksum = -1,
+                                            const void* values = nullptr,
+                                            const std::vector<uint32_t>& trailer_signatures = {}) {
+  uint64_t rows = 0;
+  if (parts.size() != lengths.size()) throw std::invalid_argument("chunk_body_host: one length per part");
+  sha256::batch_check(s3h_chunk_geometry(lengths.data(), lengths.size(), chunk_bytes, nullptr, nullptr, nullptr,
+                                         &rows, nullptr));
+  if (signatures.size() != 8 * rows || (checksum != -1 && trailer_signatures.size() != 8 * parts.size()))
+    throw std::invalid_argument("chunk_body_host: 8 words per signature and per trailer signature");
+  const ChunkBodyGeometry g = chunk_body_geometry(lengths, chunk_bytes, checksum);
+  std::vector<uint8_t> out(g.total);
+  sha256::batch_check(s3h_cpu_chunk_body(parts.data(), lengths.data(), parts.size(), chunk_bytes, signatures.data(),
+                                         checksum, values, checksum == -1 ? nullptr : trailer_signatures.data(),
+                                         out.data(), nullptr));
+  return out;
+}
+
+// Device-resident parts, one-shot and blocking: signed and framed on the device, the packed bodies
+// copied back (s3h_chunk_body_batch_device).  checksum -1, or a CRC kind.
+inline std::vector<uint8_t> chunk_body_batch_device(int device, const ChunkSignContext& ctx, int checksum,
+                                                    const void* d_base, const std::vector<uint64_t>& offsets,
+                                                    const std::vector<uint64_t>& lengths, uint64_t chunk_bytes,
+                                                    const std::vector<uint32_t>& seeds) {
+  if (offsets.size() != lengths.size() || seeds.size() != 8 * lengths.size())
+    throw std::invalid_argument("chunk_body_batch_device: one offset, one length and one 8-word seed per part");
+  const ChunkBodyGeometry g = chunk_body_geometry(lengths, chunk_bytes, checksum);
+  std::vector<uint8_t> out(g.total);
+  sha256::batch_check(s3h_chunk_body_batch_device(device, ctx.get(), checksum, d_base, offsets.data(), lengths.data(),
+                                                  lengths.size(), chunk_bytes, seeds.data(), out.data(), nullptr));
+  return out;
 }
 
 }  // namespace s3h

@@ -76,6 +76,9 @@ C_ABI_SYMBOLS = (
     "s3h_chunk_plan_create_trailer", "s3h_chunk_plan_launch_trailer", "s3h_chunk_plan_trailer",
     "s3h_chunk_plan_trailer_info", "s3h_chunk_sign_trailer_batch_device",
     "s3h_chunk_sign_trailer_batch_host",
+    # aws-chunked bodies
+    "s3h_chunk_body_geometry", "s3h_cpu_chunk_body", "s3h_chunk_plan_body", "s3h_chunk_plan_body_info",
+    "s3h_chunk_body_batch_device",
 )
 # enum s3h_trailer_checksum, and the numpy layout of one value of each kind
 TRAILER_IDS = {"crc32c": 0, "crc32": 1, "crc64nvme": 2, "sha1": 3, "sha256": 4}
@@ -479,6 +482,17 @@ def lib() -> ctypes.CDLL:
                                                             ctypes.c_uint64, ctypes.c_uint64,
                                                             ctypes.c_void_p, ctypes.c_void_p,
                                                             ctypes.c_void_p, ctypes.c_void_p]
+            L.s3h_chunk_body_geometry.argtypes = [u64p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int,
+                                                  u64p, u64p, u64p]
+            L.s3h_cpu_chunk_body.argtypes = [ctypes.POINTER(ctypes.c_void_p), u64p, ctypes.c_uint64,
+                                             ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, u64p]
+            L.s3h_chunk_plan_body.argtypes = [ctypes.c_void_p] * 6 + [u64p, ctypes.c_void_p]
+            L.s3h_chunk_plan_body_info.argtypes = [ctypes.c_void_p, u64p, u64p, u64p, u64p, u64p]
+            L.s3h_chunk_body_batch_device.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+                                                      ctypes.c_void_p, u64p, u64p, ctypes.c_uint64,
+                                                      ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+                                                      u64p]
             _lib = L
     return _lib
 

@@ -142,6 +142,50 @@ void trailer_link(const s3h_chunk_sign_ctx_s *C, const s3h::TrailerKind &K, cons
   finish(C->trailer_istate, C->ostate, tail, C->trailer_nblk, sig);
 }
 
+inline uint64_t hexlen(uint64_t k) { return k == 0 ? 1 : uint64_t(64 - __builtin_clzll(k) + 3) / 4; }
+
+// Wire length of the body of a part of `len` bytes: its framed data chunks, the final line and
+// `ending` bytes ("\r\n" or the trailer text).
+inline uint64_t body_length(uint64_t len, uint64_t chunk_bytes, uint64_t ending) {
+  const uint64_t full = len / chunk_bytes, rem = len % chunk_bytes;
+  return full * (hexlen(chunk_bytes) + 85 + chunk_bytes) + (rem ? hexlen(rem) + 85 + rem : 0) + 84 + ending;
+}
+
+// "<hex len>;chunk-signature=<64 hex>\r\n" at out (no NUL); returns its length.
+size_t frame_line(uint64_t chunk_len, const uint8_t *sig, uint8_t *out) {
+  char head[40];
+  const int at = std::snprintf(head, sizeof head, "%llx;chunk-signature=", static_cast<unsigned long long>(chunk_len));
+  std::memcpy(out, head, size_t(at));
+  put_hex(sig, 32, out + at);
+  out[at + 64] = '\r';
+  out[at + 65] = '\n';
+  return size_t(at) + 66;
+}
+
+// One part's body at out: `sigs` its data-chunk signatures and the final chunk's behind them.
+void write_body(const uint8_t *part, uint64_t len, uint64_t chunk_bytes, const uint8_t *sigs,
+                const s3h::TrailerKind *K, const void *values, uint64_t at, const uint8_t *trailer_sig,
+                uint8_t *out) {
+  uint64_t c = 0;
+  for (uint64_t done = 0; done < len; ++c) {
+    const uint64_t k = std::min(chunk_bytes, len - done);
+    out += frame_line(k, sigs + 32 * c, out);
+    std::memcpy(out, part + done, k);
+    out[k] = '\r';
+    out[k + 1] = '\n';
+    out += k + 2;
+    done += k;
+  }
+  out += frame_line(0, sigs + 32 * c, out);
+  if (K) {
+    out += trailer_line(*K, values, at, reinterpret_cast<char *>(out));
+    std::memcpy(out, "\r\nx-amz-trailer-signature:", 26);
+    put_hex(trailer_sig, 32, out + 26);
+    out += 90;
+  }
+  std::memcpy(out, K ? "\r\n\r\n" : "\r\n", K ? 4 : 2);
+}
+
 void chain(const s3h_chunk_sign_ctx_s *C, const uint8_t *digests, uint64_t chunks, const uint8_t *seed,
            uint8_t *sigs) {
   const uint8_t *prev = seed;
@@ -307,6 +351,61 @@ int s3h_chunk_header_text(uint64_t chunk_len, const uint32_t sig[8], char *out, 
   int at = std::snprintf(out, size_t(out_len), "%llx;chunk-signature=", static_cast<unsigned long long>(chunk_len));
   put_hex(reinterpret_cast<const uint8_t *>(sig), 32, reinterpret_cast<uint8_t *>(out) + at);
   std::memcpy(out + at + 64, "\r\n", 3);
+  return S3H_OK;
+}
+
+int s3h_chunk_body_geometry(const uint64_t *lengths, uint64_t n, uint64_t chunk_bytes, int checksum,
+                            uint64_t *body_lengths, uint64_t *body_offsets, uint64_t *total) {
+  const s3h::TrailerKind *K = s3h::trailer_kind(checksum);
+  if (checksum != -1 && !K) return fail(S3H_EINVAL, "chunk body geometry: unknown checksum %d", checksum);
+  if (int rc = s3h_chunk_geometry(lengths, n, chunk_bytes, nullptr, nullptr, nullptr, nullptr, nullptr)) return rc;
+  // the ending: "\r\n", or the trailer text (name ':' text, 26 + 64 bytes of signature line, two line ends)
+  const uint64_t ending = K ? std::strlen(K->name) + 1 + K->text_len + 94 : 2;
+  uint64_t sum = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    const uint64_t b = body_length(lengths[i], chunk_bytes, ending);
+    if (body_lengths) body_lengths[i] = b;
+    if (body_offsets) body_offsets[i] = sum;
+    sum += b;
+  }
+  if (total) *total = sum;
+  return S3H_OK;
+}
+
+int s3h_cpu_chunk_body(const uint8_t *const *parts, const uint64_t *lengths, uint64_t n, uint64_t chunk_bytes,
+                       const uint32_t *signatures, int checksum, const void *values,
+                       const uint32_t *trailer_signatures, uint8_t *body, const uint64_t *body_offsets) {
+  const s3h::TrailerKind *K = s3h::trailer_kind(checksum);
+  if (checksum != -1 && !K) return fail(S3H_EINVAL, "chunk body: unknown checksum %d", checksum);
+  if (!parts || !lengths || !signatures || !body) return fail(S3H_EINVAL, "chunk body: null argument");
+  if ((K != nullptr) != (values != nullptr) || (K != nullptr) != (trailer_signatures != nullptr))
+    return fail(S3H_EINVAL, "chunk body: checksum values and trailer signatures go with a checksum kind, and only with one");
+  std::vector<uint64_t> sig(n ? n : 1), packed(n ? n : 1);
+  uint64_t total = 0;
+  if (int rc = s3h_chunk_geometry(lengths, n, chunk_bytes, nullptr, sig.data(), nullptr, nullptr, nullptr)) return rc;
+  if (int rc = s3h_chunk_body_geometry(lengths, n, chunk_bytes, checksum, nullptr, packed.data(), &total)) return rc;
+  for (uint64_t i = 0; i < n; ++i)
+    if (lengths[i] && !parts[i]) return fail(S3H_EINVAL, "chunk body: part %llu is null", (unsigned long long)i);
+  const uint64_t *at = body_offsets ? body_offsets : packed.data();
+  const uint8_t *sigs = reinterpret_cast<const uint8_t *>(signatures);
+  const uint8_t *tsig = reinterpret_cast<const uint8_t *>(trailer_signatures);
+  std::atomic<uint64_t> next{0};
+  auto work = [&] {
+    for (uint64_t i; (i = next.fetch_add(1)) < n;)
+      write_body(parts[i], lengths[i], chunk_bytes, sigs + 32 * sig[i], K, values, i, K ? tsig + 32 * i : nullptr,
+                 body + at[i]);
+  };
+  int cpus = 1;
+  s3h_host_threads(1, &cpus);
+  // a thread per MiB at least: starting one costs about as much as copying that
+  const unsigned t = unsigned(std::min<uint64_t>({uint64_t(std::max(1, cpus)), n, (total >> 20) + 1}));
+  std::vector<std::thread> pool;
+  try {
+    for (unsigned k = 1; k < t; ++k) pool.emplace_back(work);
+  } catch (const std::exception &) {  // fewer threads: the ones started and this one finish
+  }
+  work();
+  for (auto &th : pool) th.join();
   return S3H_OK;
 }
 

@@ -95,8 +95,14 @@
 // wait times out (the forced-fault build `make stall`, tests/test_gpu_errors.py)
 #define S3H_EXP_STALL_PRODUCER 0
 #endif
+#ifndef S3H_EXP_BODY_XLANE
+// chunk body kernel, realignment: a lane's second source line from 0 = a second aligned load,
+// 1 = its neighbour lane's first line (a cross-lane move; lane 63 alone loads)
+#define S3H_EXP_BODY_XLANE 0
+#endif
 
 #ifndef S3H_EXPERIMENT_BUILD
+static_assert(S3H_EXP_BODY_XLANE == 0, "product build: the body kernel loads both source lines");
 static_assert(S3H_EXP_SKEW_BLK_PAD == 0, "product build: S3H_EXP_SKEW_BLK_PAD must be 0");
 static_assert(S3H_EXP_SKEW_BPS_NC2 == 8, "product build: S3H_EXP_SKEW_BPS_NC2 must be 8");
 static_assert(S3H_EXP_PRODUCER_ROLLED == 0, "product build: unrolled skew producer");

@@ -3,7 +3,7 @@
 // unit with device code), pinned host memory and device placement (pinned.cpp), and the
 // stream units' hooks.  The C-ABI itself is include/s3hash.h.
 //
-//   launch.hip    sha256_kernels.hip + sha1_kernels.hip + crc32_kernels.hip + chunk_sign_kernels.hip + chunk_trailer_kernels.hip + the hipLaunchKernelGGL calls (device code)
+//   launch.hip    sha256_kernels.hip + sha1_kernels.hip + crc32_kernels.hip + chunk_sign_kernels.hip + chunk_trailer_kernels.hip + chunk_body_kernels.hip + the hipLaunchKernelGGL calls (device code)
 //   plan.cpp      plans: kernel choice, slot sorting, launches, error words; device-resident C-ABI
 //   pinned.cpp    NUMA-placed pinned host memory, device placement, s3h_host_alloc / _numa
 //   host_path.cpp host-resident pipeline (slices, groups), per-device contexts, the merge queue
@@ -207,6 +207,9 @@ hipError_t launch_crc64_range(const s3h::Crc64Args& A, uint32_t piece_grid, hipS
 hipError_t launch_chunk_chain(const s3h::ChunkChainArgs& A, hipStream_t s);
 // The trailer signature behind it (chunk_trailer_kernels.hip): one lane per part, A.n parts.
 hipError_t launch_chunk_trailer(const s3h::ChunkTrailerArgs& A, hipStream_t s);
+// The aws-chunked bodies (chunk_body_kernels.hip): one wave per work item, A.items of them in
+// grid stride over `grid` workgroups.
+hipError_t launch_chunk_body(const s3h::ChunkBodyArgs& A, uint32_t grid, hipStream_t s);
 
 // ------------------------------------------------------------------ CRC plans (crc.cpp)
 // The host path's use of a plan: created once per context with the tables uploaded

@@ -222,6 +222,43 @@ struct ChunkTrailerArgs {
   uint32_t tail[kTrailerTailWords];  // big-endian words, the two 64-byte hex fields zeroed
 };
 
+// ------------------------------------------------------------- aws-chunked bodies (chunk_body_kernels.hip)
+// The wire form of a chunk-signed upload: per data chunk of k bytes
+//   hex(k) ";chunk-signature=" hex(sig) "\r\n" data "\r\n"          hexlen(k) + 85 + k bytes
+// then the line of the final 0-byte chunk (84 bytes) and "\r\n" or the trailer text.  One work
+// item (one wave) per piece of a data chunk -- at most kChunkBodyPiece contiguous bytes -- and one
+// per part for its final line and ending.  Every full chunk of a plan has the same wire length,
+// so chunk i of a part starts at  body offset + i * (head_len + chunk_bytes + 2).
+struct ChunkBodyPart {
+  uint64_t off;     // byte offset of the part relative to the launch's base pointer
+  uint64_t len;
+  uint64_t full;    // floor(len / chunk_bytes)
+  uint64_t item0;   // the part's first work item: full * pieces_per_chunk data items, the
+                    // remainder chunk's ceil(rem / kChunkBodyPiece), then the final item
+  uint64_t sig;     // row of the part's first signature
+};
+constexpr int kChunkBodyThreads = 256;         // 4 waves, one item each per grid pass
+constexpr uint32_t kChunkBodyPiece = 16384;    // 16 tiles of 64 lanes x 16 bytes
+constexpr uint32_t kChunkBodyMaxGrid = 2048;   // 32 waves on each of 256 CUs; more items: grid stride
+// The fixed text the kernel copies, uploaded with the plan: ";chunk-signature=" at byte 0, the
+// checksum's name and ':' at kChunkBodyNameAt, "\r\nx-amz-trailer-signature:" at kChunkBodySigAt.
+constexpr uint32_t kChunkBodyNameAt = 32, kChunkBodySigAt = 64, kChunkBodyTextBytes = 96;
+struct ChunkBodyArgs {
+  const uint8_t* base;
+  const ChunkBodyPart* parts;
+  const uint64_t* body_offs;   // n byte offsets of the bodies relative to `body`
+  const uint32_t* signatures;  // the chain kernel's
+  const void* checksums;       // trailer form: n values, uint32_t, or uint64_t when `wide`; else null
+  const uint32_t* trailer;     // trailer form: n x 8 words
+  const uint8_t* text;         // kChunkBodyTextBytes
+  uint8_t* body;
+  uint64_t n, items, chunk_bytes;
+  uint32_t pieces_per_chunk;   // ceil(chunk_bytes / kChunkBodyPiece)
+  uint32_t head_len;           // hexlen(chunk_bytes) + 83: a full chunk's bytes in front of its data
+  uint32_t wide;               // 0: 32-bit values (8 characters), 1: 64-bit values (12)
+  uint32_t name_len;           // the checksum's name and ':'
+};
+
 // ------------------------------------------------------------- synthetic input generator
 // G(seed, p, L) of SURVEY.md 8(d): one record per part (byte offset, length, generator id).
 struct GenPart { uint64_t off, len, id; };

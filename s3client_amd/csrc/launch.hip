@@ -1,5 +1,5 @@
 // launch.hip -- the only translation unit with device code: the gfx950 kernels of
-// sha256_kernels.hip, sha1_kernels.hip, crc32_kernels.hip, crc64_kernels.hip, chunk_sign_kernels.hip and chunk_trailer_kernels.hip and the launches that pick among them.  Everything around the launches --
+// sha256_kernels.hip, sha1_kernels.hip, crc32_kernels.hip, crc64_kernels.hip, chunk_sign_kernels.hip, chunk_trailer_kernels.hip and chunk_body_kernels.hip and the launches that pick among them.  Everything around the launches --
 // plans, the host pipeline, streams, routing -- is host C++ in the other units (internal.hpp).
 #include <hip/hip_runtime.h>
 
@@ -10,6 +10,7 @@
 #include "crc64_kernels.hip"
 #include "chunk_sign_kernels.hip"
 #include "chunk_trailer_kernels.hip"
+#include "chunk_body_kernels.hip"
 
 namespace s3h::host {
 
@@ -160,6 +161,11 @@ hipError_t launch_chunk_trailer(const s3h::ChunkTrailerArgs& A, hipStream_t s) {
   constexpr uint64_t per_wg = s3h::kChunkChainThreads;
   hipLaunchKernelGGL(s3h::sigv4_trailer_kernel, dim3(uint32_t((A.n + per_wg - 1) / per_wg)),
                      dim3(s3h::kChunkChainThreads), 0, s, A);
+  return hipGetLastError();
+}
+
+hipError_t launch_chunk_body(const s3h::ChunkBodyArgs& A, uint32_t grid, hipStream_t s) {
+  hipLaunchKernelGGL(s3h::chunk_body_kernel, dim3(grid), dim3(s3h::kChunkBodyThreads), 0, s, A);
   return hipGetLastError();
 }
 

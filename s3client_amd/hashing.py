@@ -771,6 +771,7 @@ class ChunkSignPlan:
                                                       _p64(self.lengths), self.n, self.chunk_bytes,
                                                       ctypes.byref(h)))
         self._h = h
+        self._body_lengths = None  # of the first body launch (s3h_chunk_plan_body_info)
 
     def info(self) -> dict:
         n, c, s, m = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
@@ -829,6 +830,41 @@ class ChunkSignPlan:
                           ("trailer_out", trailer_out, 32 * self.n, 16))
         check(lib().s3h_chunk_plan_trailer(self._h, ctx._h, *ptrs,
                                            ctypes.c_void_p(_stream_handle(stream))))
+
+    def body_info(self) -> dict:
+        """The plan's body lengths (each part's Content-Length) and their sum, and the body
+        kernel's shape: work items, the most bytes of a chunk one item copies, workgroups
+        (s3h_chunk_plan_body_info)."""
+        lens = np.zeros(self.n, dtype=np.uint64)
+        total, items, piece, grid = (ctypes.c_uint64() for _ in range(4))
+        check(lib().s3h_chunk_plan_body_info(self._h, _p64(lens), ctypes.byref(total), ctypes.byref(items),
+                                             ctypes.byref(piece), ctypes.byref(grid)))
+        return {"body_lengths": lens, "total": total.value, "items": items.value,
+                "piece_bytes": piece.value, "grid": grid.value}
+
+    def body(self, data, signatures, body, checksums=None, trailer_signatures=None, body_offsets=None,
+             stream=None) -> None:
+        """Write every part's aws-chunked body into ``body`` on ``stream`` (s3h_chunk_plan_body):
+        part p's at byte ``body_offsets[p]`` (host values; None: packed back to back), framed
+        with ``signatures`` as ``launch`` wrote them.  A trailer plan also takes ``checksums``
+        and ``trailer_signatures`` as ``launch_trailer`` wrote them and writes the trailer form.
+        Queued behind those launches on the same stream it needs no synchronisation in between.
+        Device tensors, or raw device pointers; ``body`` needs no alignment."""
+        if self._body_lengths is None:
+            self._body_lengths = self.body_info()["body_lengths"]
+        lens = self._body_lengths
+        offs = None if body_offsets is None else _u64(body_offsets)
+        if offs is not None and offs.shape != lens.shape:
+            raise ValueError("body_offsets: one offset per part")
+        need = int(lens.sum()) if offs is None else int((offs + lens).max())
+        vb = self._value_bytes()
+        args = [("data", data, _extent(self.offsets, self.lengths), 1),
+                ("signatures", signatures, 32 * self.signatures, 4)]
+        opt = [("checksums", checksums, vb * self.n, vb), ("trailer_signatures", trailer_signatures, 32 * self.n, 4)]
+        ptrs = self._ptrs(*args) + [None if a[1] is None else self._ptrs(a)[0] for a in opt] + \
+            self._ptrs(("body", body, need, 1))
+        check(lib().s3h_chunk_plan_body(self._h, *ptrs, None if offs is None else _p64(offs),
+                                        ctypes.c_void_p(_stream_handle(stream))))
 
     def status(self, stream=None) -> None:
         """Wait for ``stream``; raise if a chunk-hash launch since the last check reported a
@@ -970,6 +1006,77 @@ def chunk_sign_trailer_host(parts: Sequence, chunk_bytes: int, ctx: ChunkSignCon
                                                   int(chunk_bytes), sd.ctypes.data, sigs.ctypes.data,
                                                   vals.ctypes.data, tsig.ctypes.data))
     return sigs, vals, tsig
+
+
+def _body_kind(checksum) -> int:
+    return -1 if checksum is None else _trailer_id(checksum)
+
+
+def chunk_body_geometry(lengths, chunk_bytes: int, checksum=None) -> dict:
+    """Wire lengths of the aws-chunked bodies of parts of ``lengths`` cut at ``chunk_bytes``
+    (s3h_chunk_body_geometry, no GPU): ``body_lengths[p]`` is the Content-Length of part p's
+    request, ``body_offsets[p]`` where its body starts when they are packed back to back,
+    ``total`` their sum.  ``checksum`` None, or the trailer's kind."""
+    lens = _u64(lengths)
+    n = int(lens.size)
+    blen, boff = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
+    total = ctypes.c_uint64()
+    check(lib().s3h_chunk_body_geometry(_p64(lens), n, int(chunk_bytes), _body_kind(checksum), _p64(blen),
+                                        _p64(boff), ctypes.byref(total)))
+    return {"n": n, "body_lengths": blen, "body_offsets": boff, "total": total.value}
+
+
+def cpu_chunk_body(parts: Sequence, chunk_bytes: int, signatures, checksum=None, values=None,
+                   trailer_signatures=None, out=None, body_offsets=None) -> np.ndarray:
+    """The aws-chunked bodies of host-resident parts on the CPU (s3h_cpu_chunk_body):
+    ``signatures`` as ``cpu_chunk_signatures`` returns them; with ``checksum`` also ``values``
+    (n checksums in the kind's layout) and ``trailer_signatures`` (n, 8).  Part p's body goes to
+    ``out[body_offsets[p]:]`` (a uint8 array; None: a new one) -- ``body_offsets`` None: packed
+    back to back.  Returns ``out``."""
+    arrs, ptrs, lens = _host_parts(parts)
+    n = len(arrs)
+    kind = _body_kind(checksum)
+    sig = _words(signatures, None, "signatures")
+    # (values without a kind: the library refuses them)
+    vals = None if values is None else _trailer_values(kind, values, None) if kind >= 0 else np.ascontiguousarray(values)
+    tsig = None if trailer_signatures is None else _words(trailer_signatures, None, "trailer signatures")
+    offs = None if body_offsets is None else _u64(body_offsets)
+    g = chunk_body_geometry(lens, chunk_bytes, checksum)
+    need = g["total"] if offs is None else int((offs + g["body_lengths"]).max())
+    if out is None:
+        out = np.zeros(need, dtype=np.uint8)
+    if out.dtype != np.uint8 or not out.flags.c_contiguous or out.size < need:
+        raise ValueError(f"out must be a contiguous uint8 array of at least {need} bytes")
+    if sig.shape[0] != chunk_geometry(lens, chunk_bytes)["signatures"]:
+        raise ValueError("signatures: one row per data chunk and one more per part")
+    check(lib().s3h_cpu_chunk_body(ptrs, _p64(lens), n, int(chunk_bytes), sig.ctypes.data, kind,
+                                   None if vals is None else vals.ctypes.data,
+                                   None if tsig is None else tsig.ctypes.data, out.ctypes.data,
+                                   None if offs is None else _p64(offs)))
+    return out
+
+
+def chunk_body_batch_device(data, offsets, lengths, chunk_bytes: int, ctx: ChunkSignContext, seeds,
+                            trailer: str | None = None, out=None, body_offsets=None) -> np.ndarray:
+    """One-shot: sign the chunks of device-resident parts and frame them on the device, then copy
+    the bodies back (s3h_chunk_body_batch_device).  ``trailer`` None for the plain form, or
+    "crc32c", "crc32", "crc64nvme".  Returns host uint8: the bodies packed back to back, or at
+    ``body_offsets`` in ``out``."""
+    offs, lens = _u64(offsets), _u64(lengths)
+    n = int(lens.size)
+    sd = _words(seeds, n, "seeds")
+    boffs = None if body_offsets is None else _u64(body_offsets)
+    g = chunk_body_geometry(lens, chunk_bytes, trailer)
+    need = g["total"] if boffs is None else int((boffs + g["body_lengths"]).max())
+    if out is None:
+        out = np.zeros(need, dtype=np.uint8)
+    if out.dtype != np.uint8 or not out.flags.c_contiguous or out.size < need:
+        raise ValueError(f"out must be a contiguous uint8 array of at least {need} bytes")
+    d_base = _device_buffer("data", data, _extent(offs, lens))
+    check(lib().s3h_chunk_body_batch_device(data.device.index or 0, ctx._h, _body_kind(trailer), d_base,
+                                            _p64(offs), _p64(lens), n, int(chunk_bytes), sd.ctypes.data,
+                                            out.ctypes.data, None if boffs is None else _p64(boffs)))
+    return out
 
 
 class Crc64Plan(CrcPlan):

@@ -67,6 +67,8 @@ ALL_KERNELS = {
     "chunk-chain": "_ZN3s3h24sigv4_chunk_chain_kernelENS_14ChunkChainArgsE",
     # SigV4 trailer signature (chunk_trailer_kernels.hip): code hash only
     "chunk-trailer": "_ZN3s3h20sigv4_trailer_kernelENS_16ChunkTrailerArgsE",
+    # aws-chunked bodies (chunk_body_kernels.hip): code hash only
+    "chunk-body": "_ZN3s3h17chunk_body_kernelENS_13ChunkBodyArgsE",
 }
 FLAG_KERNELS = ("skew_nc2", "skews", "dual_group", "dual_group_skew", "dual_group_mixed")
 ERR_STORE = re.compile(r"^\t(global|flat|buffer)_atomic_or\b")
