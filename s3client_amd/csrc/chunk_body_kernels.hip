@@ -22,7 +22,9 @@
 // once.  The text -- lengths, signatures, checksum -- is rendered a character per lane with hex4
 // and base64_4 of the chain and trailer kernels and stored as bytes.
 //
-// S3H_EXP_BODY_XLANE (experiment builds): a lane's second line is its neighbour lane's first.
+// A lane loads its second source line itself: taking it from the neighbour lane's first (a
+// cross-lane move, lane 63 alone loading) measured 4 % slower on C2 and needs 14 more VGPRs
+// (profiles/chunk_body_c2.json).
 //
 // The kernel lives in a text section of its own, so the machine code of the kernels pinned in
 // s3client_amd/kernel_isa_counts.json stays as it is.
@@ -65,13 +67,6 @@ __device__ __forceinline__ uint4 realign(const uint4& lo, const uint4& hi, uint3
                     __builtin_amdgcn_alignbyte(x[Q + 3], x[Q + 2], r), __builtin_amdgcn_alignbyte(x[Q + 4], x[Q + 3], r));
 }
 
-#if S3H_EXP_BODY_XLANE
-__device__ __forceinline__ uint4 next_lane(const uint4& v) {
-  return make_uint4(__shfl_down(v.x, 1, 64), __shfl_down(v.y, 1, 64), __shfl_down(v.z, 1, 64),
-                    __shfl_down(v.w, 1, 64));
-}
-#endif
-
 // Destination lines q[0 .. nb) from source lines p[0 .. nb] at byte shift 4 * Q + r; `two`: the
 // shift is not zero, so line i also takes bytes of p[i + 1].
 template <int Q>
@@ -82,14 +77,7 @@ __device__ __forceinline__ void copy_lines(const uint4* p, uint4* q, uint32_t nb
     const uint32_t i = t + lane;
     const uint4 a0 = p[i], a1 = p[i + 64], a2 = p[i + 128], a3 = p[i + 192];
     uint4 b0 = a0, b1 = a1, b2 = a2, b3 = a3;
-#if S3H_EXP_BODY_XLANE
-    if (two) {
-      b0 = next_lane(a0), b1 = next_lane(a1), b2 = next_lane(a2), b3 = next_lane(a3);
-      if (lane == 63) b0 = p[i + 1], b1 = p[i + 65], b2 = p[i + 129], b3 = p[i + 193];
-    }
-#else
     if (two) b0 = p[i + 1], b1 = p[i + 65], b2 = p[i + 129], b3 = p[i + 193];
-#endif
     q[i] = realign<Q>(a0, b0, r);
     q[i + 64] = realign<Q>(a1, b1, r);
     q[i + 128] = realign<Q>(a2, b2, r);
@@ -97,22 +85,11 @@ __device__ __forceinline__ void copy_lines(const uint4* p, uint4* q, uint32_t nb
   }
   for (; t < nb; t += 64) {
     const uint32_t i = t + lane;
-#if S3H_EXP_BODY_XLANE
-    uint4 a = make_uint4(0, 0, 0, 0);
-    if (i < nb + (two ? 1u : 0u)) a = p[i];  // (line nb holds bytes of destination line nb - 1)
-    uint4 b = a;
-    if (two) {
-      b = next_lane(a);
-      if (lane == 63 && i < nb) b = p[i + 1];
-    }
-    if (i < nb) q[i] = realign<Q>(a, b, r);
-#else
     if (i < nb) {
       const uint4 a = p[i];
       const uint4 b = two ? p[i + 1] : a;
       q[i] = realign<Q>(a, b, r);
     }
-#endif
   }
 }
 

@@ -570,11 +570,7 @@ int run_host_shard(HostCtx& C, const HostShard& sh, const int* algos, int nalgo,
   // U[1, 8] MiB: 24.3 -> 27.8).
   if (!staged && !uniform && n > kPinnedStageMin) staged = true;
   // Too many pageable parts for the staging cap even at 64 B per slice: pageable DMAs.
-#ifdef S3H_EXP_PAGEABLE_DIRECT  // tools/ experiment builds only: pageable DMAs, no staging
-  bool direct_pageable = staged && parts;
-#else
   bool direct_pageable = staged && parts && n * 64 > kStageSlot;
-#endif
   if (direct_pageable) staged = false;
   if (slice == 0)
     slice = staged ? std::max<uint64_t>(std::max<uint64_t>(64, kStageSlot / n / 64 * 64),
@@ -651,11 +647,9 @@ int run_host_shard(HostCtx& C, const HostShard& sh, const int* algos, int nalgo,
   // full-slice hash ran past the copies (tools/host_timeline.py trace).
   auto slice_blocks = [&](uint64_t b0) -> uint64_t {
     const uint64_t left = max_blocks - b0;
-#ifndef S3H_EXP_NO_TAIL_RAMP  // tools/ experiment builds only: round-3 fixed slices
-    constexpr uint64_t D = S3H_EXP_TAIL_RAMP_DIV;
+    constexpr uint64_t D = 8;
     if (bps >= 256 && left < D * bps)
       return std::min(left, std::max<uint64_t>(bps / 16, (left + D - 1) / D));
-#endif
     return std::min(left, bps);
   };
   for (uint64_t b0 = 0, step = 0; b0 < max_blocks && rc == S3H_OK; b0 += step, ++k) {

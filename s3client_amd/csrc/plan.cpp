@@ -38,9 +38,6 @@ constexpr uint64_t kPcMaxParts = 65536;
 // Skew / quad kernels: consumer waves per workgroup -- the fewest that keep the grid within
 // one workgroup per CU (256): one up to 2,048 parts, two up to 4,096 (kQuadMaxParts).
 int quad_waves(uint64_t n) {
-#ifdef S3H_EXP_FORCE_NC  // tools/ experiment builds only
-  return S3H_EXP_FORCE_NC;
-#endif
   return n <= 256ull * s3h::kQuadChainsPerWave ? 1 : 2;
 }
 
@@ -219,7 +216,7 @@ int device_cus(int device) {  // cached: the host pipeline asks once per slice
 
 // Both digests of 2,049-8,192 parts (sha256_md5_group_kernel) run every chain at skewp's rate
 // beside a self-fed MD5 wave: ~2,550 cycles per block on the C4 shard's equal parts (457 GiB/s
-// for both), planned at 2,650 for ragged groups (exp_config.hpp S3H_EXP_DUAL_SKEWP_CYC).  A
+// for both), planned at 2,650 for ragged groups (kDualSkewpCyc below).  A
 // ragged batch is timed by its longest parts, so sha256_md5_group_mixed_kernel gives the
 // longest F x 8 slots skew groups and the rest skewp groups: F = the fewest 8-slot groups
 // after which every remaining part, at the skewp rate, ends before the longest part does at
@@ -229,14 +226,18 @@ int device_cus(int device) {  // cached: the host pipeline asks once per slice
 // (profiles/r04_exp_dual_mixed_apart.jsonl); when that grid does not fit one workgroup per
 // CU, each skew group keeps its MD5 wave (~2,280 cycles per block; round 3's form).  0 (the
 // plain group kernel) when neither fits (e.g. equal lengths) or there is nothing to gain.
+// Cycles per block of a skewp group beside its MD5 wave, and of a skew group with its MD5
+// apart / beside it -- the rates the split into skew and skewp groups is planned with.  2,650
+// from a sweep on C3 (profiles/r06_dual_mixed_planning_sweep.json: 2,550, calibrated on the C4
+// shard's equal parts, left C3's ragged skewp groups finishing last).
+constexpr double kDualSkewpCyc = 2650, kDualSkewCycApart = 2224, kDualSkewCycInGroup = 2280;
 uint32_t dual_mixed_solo(const s3h::Slot* slots, uint64_t n, uint64_t cus, bool* apart) {
   constexpr uint64_t kSkew = 8, kSkewp = 32;
   *apart = false;
   if (n <= 2048 || cus == 0 || (n + kSkewp - 1) / kSkewp > cus) return 0;
   const double longest = double(s3h::nblocks(slots[0].len));
-  for (int a = S3H_EXP_MIXED_MD5_APART; a >= 0; --a) {
-    const double ratio = a ? double(S3H_EXP_DUAL_SKEWP_CYC) / S3H_EXP_DUAL_SKEW_CYC_APART
-                           : double(S3H_EXP_DUAL_SKEWP_CYC) / S3H_EXP_DUAL_SKEW_CYC_INGROUP;
+  for (int a = 1; a >= 0; --a) {  // the apart form first
+    const double ratio = kDualSkewpCyc / (a ? kDualSkewCycApart : kDualSkewCycInGroup);
     uint64_t lo = 0, hi = n;  // first slot whose part ends in time at the skewp rate
     while (lo < hi) {
       const uint64_t mid = (lo + hi) / 2;
@@ -315,11 +316,7 @@ int plan_geometry(s3h_plan_s* P, const uint64_t* offsets, const uint64_t* length
   P->quad_waves = quad_waves(n);
   P->solo = 0;
   if (P->kernel == S3H_KERNEL_SKEW && P->quad_waves == 2) {
-#ifdef S3H_EXP_SOLO  // tools/ experiment builds only: force the solo count
-    P->solo = uint32_t(std::min<uint64_t>(S3H_EXP_SOLO, (n + 7) / 8));
-#else
     P->solo = plan_solo(h_slots, n, uint64_t(device_cus(P->device)));
-#endif
   }
   P->dual_solo = P->algo == S3H_ALGO_SHA256
                      ? dual_mixed_solo(h_slots, n, uint64_t(device_cus(P->device)), &P->dual_apart) : 0;
@@ -420,14 +417,9 @@ DualMode dual_mode(const s3h_plan_s* S, const s3h_plan_s* M, uint64_t b0, uint64
       S->n != M->n)
     return kDualNone;
   const uint64_t cus = uint64_t(device_cus(S->device));
-#ifdef S3H_EXP_GROUP_SKEW  // tools/ experiment builds only: skew-layout group kernel
-  if (S->kernel == S3H_KERNEL_SKEW && S->quad_waves == 1 && S->grid <= cus) return kDualGroupSkew;
-#endif
-#ifndef S3H_EXP_NO_SPLIT  // tools/ experiment builds only: never the split grid
   if (S->kernel == S3H_KERNEL_SKEW && S->quad_waves == 1 &&
-      S->grid + s3h::split_md5_wgs(S->grid, S->n) <= cus)
+      S->grid + s3h::split_md5_wgs(S->n) <= cus)
     return kDualSplit;
-#endif
   // skew plans whose split grid does not fit (1,817-2,048 parts on 256 CUs): each skew group
   // with a self-fed MD5 wave over the same 8 parts, one workgroup per CU -- both digests in
   // ~125 ms for 8 MiB parts vs 140 on the skewp group kernel (profiles/r02_exp_dual_group_skew.jsonl)
@@ -437,15 +429,7 @@ DualMode dual_mode(const s3h_plan_s* S, const s3h_plan_s* M, uint64_t b0, uint64
   // two-stream form runs MD5 workgroups on CUs already running SHA-256 ones)
   const bool group_ok = S->kernel == S3H_KERNEL_SKEWP || S->kernel == S3H_KERNEL_SKEWS ||
                         S->kernel == S3H_KERNEL_SKEW;
-#ifdef S3H_EXP_NO_GROUP_NC2  // tools/ experiment builds only: round-2 behaviour
-  if (S->kernel == S3H_KERNEL_SKEW) return kDualNone;
-#endif
-#ifndef S3H_EXP_NO_DUAL_MIXED  // tools/ experiment builds only: round-2/3 behaviour
   if (group_ok && S->dual_solo > 0) return kDualGroupMixed;
-#endif
-#ifdef S3H_EXP_GROUP_ANY  // tools/ experiment builds only: the group kernel at any grid size
-  if (group_ok || S->kernel == S3H_KERNEL_PAIR || S->kernel == S3H_KERNEL_PC) return kDualGroup;
-#endif
   if (group_ok && (S->n + 31) / 32 <= cus) return kDualGroup;
   return kDualNone;
 }
@@ -463,26 +447,8 @@ int dual_launch(s3h_plan_s* S, s3h_plan_s* M, const void* d_base, uint32_t* d_sh
                                       origin, 0, nullptr);
   const s3h::LaunchArgs B = make_args(M, d_base, d_md5, ranged ? M->d_state : nullptr, b0, b1,
                                       origin, 0, nullptr);
-  uint64_t* progress = nullptr;
-  uint32_t epoch = 0;
-  if (s3h::kMd5XcdPace && ((mode == kDualGroupMixed && S->dual_apart) || mode == kDualSplit)) {
-    // the skew groups' producer step counts (F <= CUs groups in the mixed grid, sha_grid <= CUs
-    // in the split grid; slot (g % 8) * 128 + g / 8); zeroed once, then every launch tags its
-    // counts with a new epoch
-    constexpr uint64_t kProgressSlots = 1024;
-    const uint64_t groups = mode == kDualSplit ? S->grid : S->dual_solo;
-    if (groups > kProgressSlots)
-      return fail(S3H_EINVAL, "dual grid: %llu skew groups", (unsigned long long)groups);
-    if (!S->d_progress) {
-      HIP_TRY(hipMalloc(&S->d_progress, kProgressSlots * sizeof(uint64_t)));
-      HIP_TRY(hipMemsetAsync(S->d_progress, 0, kProgressSlots * sizeof(uint64_t), stream));
-    }
-    if (++S->progress_epoch == 0) S->progress_epoch = 1;
-    progress = S->d_progress;
-    epoch = S->progress_epoch;
-  }
   (void)hipGetLastError();
-  HIP_TRY(launch_dual_kernel(mode, S, M, A, B, progress, epoch, stream));
+  HIP_TRY(launch_dual_kernel(mode, S, M, A, B, stream));
   return S3H_OK;
 }
 
@@ -586,7 +552,6 @@ int s3h_plan_destroy(s3h_plan_t P) {
   (void)hipFree(P->d_state);
   (void)hipFree(P->d_zero);
   (void)hipFree(P->d_err);
-  (void)hipFree(P->d_progress);
   delete P;
   return S3H_OK;
 }

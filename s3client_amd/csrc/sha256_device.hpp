@@ -130,20 +130,12 @@ __device__ __forceinline__ void fetch_full(const uint8_t* p, bool ok, const uint
   gv4u32* q = reinterpret_cast<gv4u32*>(a & ~uintptr_t(3));
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-#ifdef S3H_EXP_NONTEMPORAL_FETCH  // experiment: round 1-3's non-temporal loads
-    const v4u32 v = __builtin_nontemporal_load(q + i);
-#else
     const v4u32 v = q[i];
-#endif
     r.d[4 * i + 0] = v.x; r.d[4 * i + 1] = v.y; r.d[4 * i + 2] = v.z; r.d[4 * i + 3] = v.w;
   }
   gu32* x = reinterpret_cast<gu32*>((a & 3) ? reinterpret_cast<uintptr_t>(q + 4)
                                              : reinterpret_cast<uintptr_t>(zero));
-#ifdef S3H_EXP_NONTEMPORAL_FETCH
-  r.d[16] = __builtin_nontemporal_load(x);
-#else
   r.d[16] = *x;
-#endif
 }
 
 // v_perm selector turning {d[j+1]:d[j]} into the big-endian word at byte shift `sh`.

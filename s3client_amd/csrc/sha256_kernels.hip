@@ -42,12 +42,8 @@
 // (kNoPad | kResume) and a final padded launch with each message's total bit length.
 #include "sha256_device.hpp"
 
-// Experiment switches and their product values: exp_config.hpp (included by sha256_device.hpp).
-#if S3H_EXP_PRODUCER_ROLLED
-#define S3H_PROD_UNROLL _Pragma("unroll 1")
-#else
-#define S3H_PROD_UNROLL _Pragma("unroll")
-#endif
+// Build switches (the forced-fault build, the generators' entry hooks): exp_config.hpp
+// (included by sha256_device.hpp).
 
 namespace s3h {
 
@@ -672,13 +668,13 @@ struct SkewGeom {
   // Blocks per producer step: 8 when the producer's lanes make at most two (part, block)
   // items per step (one step of prefetch = ~8 blocks of chain time, one sync per 8 blocks);
   // fewer for wider groups, whose producer would spill.
-  static constexpr uint32_t kBps = PAIR ? 4 : NC >= 4 ? 2 : NC == 2 ? S3H_EXP_SKEW_BPS_NC2 : 8;
+  static constexpr uint32_t kBps = PAIR ? 4 : NC >= 4 ? 2 : 8;
   static constexpr uint32_t kCols = kParts + 1;  // column kParts holds ones (read by the a-quads)
   // uint4s of padding after each block's 16 rows (skew layout).  A block is 16 x 9 uint4 =
   // 576 dwords = 0 mod 64 banks, so the producer's lanes (8 parts x 8 blocks) write each W+K
   // word 8-way bank-conflicted; 8 uint4 (128 B) would halve that, but the C4 shard runs the same
   // 2,243.6 cycles/block either way (profiles/r02_exp_skews_lds.jsonl): kept at 0.
-  static constexpr uint32_t kBlkPad = PAIR ? 0 : S3H_EXP_SKEW_BLK_PAD;
+  static constexpr uint32_t kBlkPad = 0;
   static constexpr uint32_t kBlkStride = 16 * kCols + kBlkPad;  // uint4 between blocks
 };
 // wk[buffer][block of the step][row * kCols + part] (+ kBlkPad after each block)
@@ -826,18 +822,6 @@ __device__ __forceinline__ void produce_block_simple(const RawBlock& r,
   uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = w[4], w5 = w[5], w6 = w[6], w7 = w[7],
            w8 = w[8], w9 = w[9], w10 = w[10], w11 = w[11], w12 = w[12], w13 = w[13], w14 = w[14],
            w15 = w[15];
-#ifdef S3H_EXP_PROD_ROWS  // experiment: one asm statement and one ds_write_b128 per W+K row
-  uint32_t l0_0 = 0, l0_1 = 0, l0_2 = 0, l0_3 = 0, l0_4 = 0, l0_5 = 0, l0_6 = 0, l0_7 = 0, l0_8 = 0,
-           l0_9 = 0, l0_10 = 0, l0_11 = 0, l0_12 = 0, l0_13 = 0, l0_14 = 0, l0_15 = 0, l1_0 = 0,
-           l1_1 = 0, l1_2 = 0, l1_3 = 0, c0, c1, c2, c3, c4, c5, s0, s1, s2, s3, rk0, rk1, rk2, rk3;
-  (void)la;
-#define S3H_ROW(q)                                                                        \
-  asm volatile(S3H_ALIGN8 S3H_PROD_ROW_##q : S3H_PROD_ROW_OUTS);                         \
-  buf[q][lane] = make_uint4(rk0, rk1, rk2, rk3);
-  S3H_ROW(0) S3H_ROW(1) S3H_ROW(2) S3H_ROW(3) S3H_ROW(4) S3H_ROW(5) S3H_ROW(6) S3H_ROW(7)
-  S3H_ROW(8) S3H_ROW(9) S3H_ROW(10) S3H_ROW(11) S3H_ROW(12) S3H_ROW(13) S3H_ROW(14) S3H_ROW(15)
-#undef S3H_ROW
-#else
   S3H_PROD_SIMPLE_TEMPS
   const uint32_t bsel = 0x00010203u;  // v_perm byte swap (tools/gen_producer.py --perm-bswap only)
 #ifdef S3H_PROD_ZYV
@@ -847,21 +831,14 @@ __device__ __forceinline__ void produce_block_simple(const RawBlock& r,
   asm volatile(S3H_ALIGN8 S3H_PROD_SIMPLE_ASM : S3H_PROD_SIMPLE_OUTS : [la] "v"(la), [bsel] "v"(bsel)
                : "memory");
 #endif
-#endif
 }
 
 // SIMPLE: the producer is written in the co-issuable instruction classes (it shares its
-// consumer's SIMD: sha256_skew_shared_kernel).  GPROG: the producer also stores each published
-// step count, tagged (epoch << 32 | steps), to `gprog` when it is non-null -- the pacing hint
-// of MD5 waves on other workgroups of the same XCD (ShaPacer): a plain store, which stays in
-// this XCD's L2 where those waves' L2-served polls read it (an agent-scope store would write
-// through to memory and drop the line, and every poll would then cross the fabric); one 8-byte
-// store per step, never read back by this group.
-template <int NC, bool PAIR, bool FLAGS, bool SIMPLE = false, bool GPROG = false>
+// consumer's SIMD: sha256_skew_shared_kernel).
+template <int NC, bool PAIR, bool FLAGS, bool SIMPLE = false>
 __device__ __forceinline__ void skew_body(const LaunchArgs& A, const uint32_t group,
                                           const uint32_t role, SkewLds<NC, PAIR>& L,
-                                          uint32_t* flags, uint64_t* gprog = nullptr,
-                                          uint32_t epoch = 0) {
+                                          uint32_t* flags) {
   static_assert(!FLAGS || NC == 1, "flag-synchronised groups have one consumer wave");
   using G = SkewGeom<NC, PAIR>;
   constexpr uint32_t kCpw = G::kCpw, kParts = G::kParts, kBps = G::kBps, kCols = G::kCols;
@@ -878,11 +855,6 @@ __device__ __forceinline__ void skew_body(const LaunchArgs& A, const uint32_t gr
       if (!S3H_EXP_STALL_PRODUCER || (m) <= 1u) flag_publish(&flags[0], (m)); \
     } else {                                                                  \
       __syncthreads();                                                        \
-    }                                                                         \
-    if constexpr (GPROG && !S3H_EXP_GPROG_OFF) {                              \
-      if (gprog)                                                              \
-        __hip_atomic_store(gprog, (uint64_t(epoch) << 32) | uint64_t(m),      \
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   \
     }                                                                         \
   } while (0)
 
@@ -954,16 +926,6 @@ __device__ __forceinline__ void skew_body(const LaunchArgs& A, const uint32_t gr
 #pragma unroll
     for (uint32_t r = 0; r < kItems; ++r) S3H_PRODUCE(ra[r], za[r], r, p[r], bh[r], rows(0, h[r]));
     S3H_SYNC_PRODUCED(1u);
-#ifdef S3H_EXP_PRODUCER_IDLE  // experiment (power): after step 0 the shared-SIMD producer only
-                              // keeps the flag protocol; the consumers hash stale W+K
-    if constexpr (FLAGS && SIMPLE) {
-      for (uint64_t k = 1; k <= steps; ++k) {
-        if (k < steps && k >= 2) flag_wait_ge(&flags[1], uint32_t(k - 1), alive, A.err);
-        S3H_SYNC_PRODUCED(uint32_t(k + 1));
-      }
-      return;
-    }
-#endif
     // Step k goes into buffer k & 1, which held step k - 2: FLAGS waits until the consumer
     // has released that step (the barrier of the other mode orders the same thing).
     for (uint64_t k = 1; k <= steps; k += 2) {
@@ -971,7 +933,7 @@ __device__ __forceinline__ void skew_body(const LaunchArgs& A, const uint32_t gr
         if constexpr (FLAGS) {
           if (k >= 2) flag_wait_ge(&flags[1], uint32_t(k - 1), alive, A.err);
         }
-        S3H_PROD_UNROLL
+#pragma unroll
         for (uint32_t r = 0; r < kItems; ++r) {
           fetch_full(p[r] + kStride * (k + 1), bh[r] + kBps * (k + 1) < fend[r], A.zero, ra[r]);
           S3H_FETCH_ZY(p[r] + kStride * (k + 1), bh[r] + kBps * (k + 1) < fend[r], za[r]);
@@ -982,7 +944,7 @@ __device__ __forceinline__ void skew_body(const LaunchArgs& A, const uint32_t gr
       if (k + 1 > steps) break;
       if (k + 1 < steps) {
         if constexpr (FLAGS) flag_wait_ge(&flags[1], uint32_t(k), alive, A.err);
-        S3H_PROD_UNROLL
+#pragma unroll
         for (uint32_t r = 0; r < kItems; ++r) {
           fetch_full(p[r] + kStride * (k + 2), bh[r] + kBps * (k + 2) < fend[r], A.zero, rb[r]);
           S3H_FETCH_ZY(p[r] + kStride * (k + 2), bh[r] + kBps * (k + 2) < fend[r], zb[r]);
@@ -998,19 +960,6 @@ __device__ __forceinline__ void skew_body(const LaunchArgs& A, const uint32_t gr
 #undef S3H_FETCH_ZY
 #undef S3H_SYNC_PRODUCED
   // ------------------------------------------------------------------ consumer
-#ifdef S3H_EXP_LONE_CONSUMER  // experiment: only consumer wave 0 works (wrong digests)
-  if (role != 0) return;
-#endif
-#ifdef S3H_EXP_CONSUMER_IDLE  // experiment (power): the shared-SIMD consumers only keep the
-                              // flag protocol; the producers run alone (wrong digests)
-  if constexpr (FLAGS && SIMPLE) {
-    for (uint32_t j = 0; j < uint32_t(steps); ++j) {
-      flag_wait_ge(&flags[0], j + 1, alive, A.err);
-      flag_publish(&flags[1], j + 1);
-    }
-    return;
-  }
-#endif
   __builtin_amdgcn_s_setprio(3);
   const bool ahalf = (lane >> 2) & 1u;
   const uint32_t k4 = lane & 3u;
@@ -1109,18 +1058,17 @@ __device__ __forceinline__ void skew_body(const LaunchArgs& A, const uint32_t gr
   // block is two statements instead of three -- 543.88 -> 542.38 instructions per block, C2
   // 2,207.1 -> 2,202.8 cycles per block and C4 skews 2,238.3 -> 2,232.4 in one lease; the lane
   // pair layout (skewp) measured 2,476.1 -> 2,485.5 that way and keeps the three statements
-  // (profiles/r06_skew_merge_next_ab.json).  S3H_EXP_SKEW_MERGE_NEXT: 0 never, 2 also skewp.
-  constexpr bool kMergeNext = PAIR ? S3H_EXP_SKEW_MERGE_NEXT == 2 : S3H_EXP_SKEW_MERGE_NEXT >= 1;
-  // Flag-synchronised groups (S3H_EXP_FLAG_PREFETCH, on in the product): the producer's step counter is
-  // read without waiting, just before the next step's rows (LDS executes a wave's reads in
-  // order, and the producer publishes a step only after its rows are written, so rows read
-  // after a counter value that covers the step are that step's rows); it is checked after
-  // rounds 0-15, and only a counter that did not cover the step costs a wait and a second read
-  // of the rows.  Saves the counter read's latency at every step boundary: C3 2,217 -> 2,200
-  // cycles per block, C4 skews 2,232 -> 2,220 (profiles/r06_flag_prefetch_ab.json).
-  constexpr bool kFlagPrefetch = FLAGS && S3H_EXP_FLAG_PREFETCH != 0;
+  // (profiles/r06_skew_merge_next_ab.json).
+  constexpr bool kMergeNext = !PAIR;
+  // Flag-synchronised groups of that layout (FLAGS): the producer's step counter is read
+  // without waiting, just before the next step's rows (LDS executes a wave's reads in order,
+  // and the producer publishes a step only after its rows are written, so rows read after a
+  // counter value that covers the step are that step's rows); it is checked after rounds 0-15,
+  // and only a counter that did not cover the step costs a wait and a second read of the rows.
+  // Saves the counter read's latency at every step boundary: C3 2,217 -> 2,200 cycles per
+  // block, C4 skews 2,232 -> 2,220 (profiles/r06_flag_prefetch_ab.json).
 #define S3H_SKEW_FAST(L, P, CUR, NXT)                                                           \
-  if constexpr (kMergeNext && kFlagPrefetch) {                                                  \
+  if constexpr (kMergeNext && FLAGS) {                                                          \
     /* the producer's step counter is read with the rows, checked after rounds 0-15 */          \
     uint32_t seen_prod = 0xffffffffu;                                                           \
     if (i == kBps - 1) {                                                                        \
@@ -1524,38 +1472,19 @@ __device__ __forceinline__ void md5_block_streamed(uint32_t s0, uint32_t s1, uin
 }
 
 // The consumer's fast step: all kBps blocks of one producer step, fed forward, in ONE asm
-// statement generated by tools/gen_md5.py (rows in fixed registers v[200:231] that never leave
-// the statement; rows 0-1 of block 0 pinned to v[232:239], loaded after the step's barrier).
-// The per-block statements above cost a wait state plus an alignment s_nop at each of their
-// boundaries; this has one boundary per step.  `ad`: row 0 of block 0 of the step's buffer.
-// Not for kBps = 1 (md5_pc_kernel<1>, several workgroups per CU): the fixed registers would
-// raise its 128 VGPRs to 240 and cost it occupancy.
+// statement generated by tools/gen_md5.py.  The per-block statements above cost a wait state
+// plus an alignment s_nop at each of their boundaries; this has one boundary per step.  `ad`:
+// row 0 of block 0 of the step's buffer.  Not for kBps = 1 (md5_pc_kernel<1>, several
+// workgroups per CU): the fixed registers would raise its 128 VGPRs and cost it occupancy.
 #ifdef S3H_EXP_MD5_INC  // experiment builds: another generated schedule (tools/gen_md5.py)
 #include S3H_EXP_MD5_INC
 #else
 #include "md5_step_asm.inc"
 #endif
-#define S3H_MD5_STEP_OPERANDS                                                                 \
-  : [s0] "+v"(s0), [s1] "+v"(s1), [s2] "+v"(s2), [s3] "+v"(s3), [a] "=&v"(a), [b] "=&v"(b),   \
-    [c] "=&v"(c), [d] "=&v"(d), [f] "=&v"(f), [t] "=&v"(t), "+{v[232:235]}"(r0),              \
-    "+{v[236:239]}"(r1)                                                                       \
-  : [ad] "v"(ad)                                                                              \
-  : S3H_MD5_STEP_CLOBBERS, "memory"
-template <int kBps>
-__device__ __forceinline__ void md5_step_fused(uint32_t& s0, uint32_t& s1, uint32_t& s2,
-                                               uint32_t& s3, v4u32& r0, v4u32& r1, uint32_t ad) {
-  uint32_t a, b, c, d, f, t;
-  static_assert(kBps == 2 || kBps == 4, "fused MD5 steps are generated for 2 and 4 blocks");
-  if constexpr (kBps == 4)
-    asm volatile(S3H_ALIGN8 S3H_MD5_STEP_ASM_4 S3H_MD5_STEP_OPERANDS);
-  else
-    asm volatile(S3H_ALIGN8 S3H_MD5_STEP_ASM_2 S3H_MD5_STEP_OPERANDS);
-}
-#undef S3H_MD5_STEP_OPERANDS
 
-// The rolling form of the fused step (tools/gen_md5.py roll_text, round 3): the statement reads
-// every row itself, ROLL_DEPTH rows ahead into a ring of fixed registers, with counted waits
-// every 4 rows -- no row read has less than ~20 steps to land, block boundaries included.
+// The statement's rolling form (tools/gen_md5.py roll_text, round 3): it reads every row
+// itself, ROLL_DEPTH rows ahead into a ring of fixed registers, with counted waits every 4
+// rows -- no row read has less than ~20 steps to land, block boundaries included.
 template <int kBps>
 __device__ __forceinline__ void md5_step_roll(uint32_t& s0, uint32_t& s1, uint32_t& s2,
                                               uint32_t& s3, uint32_t ad) {
@@ -1655,86 +1584,30 @@ __device__ __forceinline__ void md5_produce(const RawBlock& r, uint32_t sel, con
 // has published step B / kPaceBps, i.e. after its own load of B was issued, microseconds
 // earlier on the same CU: the MD5 read hits the CU's L1 or L2.  Pacing is a cache policy, not
 // a dependency -- the MD5 digests never read the producer's output -- so a wait longer than
-// kPaceWaitTicks just stops pacing for the rest of the launch.
-//
-// kXcd (experiment S3H_EXP_MD5_XCD_PACE; MD5 chains of skew groups that run on OTHER
-// workgroups: the mixed grid's apart MD5 workgroups, the split grid's MD5 workgroups):
-// workgroups b and b + 8 share an XCD (and its L2; MI355X_MICROARCH.md "Workgroup dispatch",
-// tools/xcd_probe.hip), so an MD5 workgroup takes the skew groups of its own class
-// blockIdx.x (mod 8) -- XcdChains -- and follows their producers' step counts in global
-// memory (ShaPacer, skew_body GPROG).
+// kPaceWaitTicks just stops pacing for the rest of the launch.  Only waves of the producer's
+// own workgroup are paced: following producers of other workgroups through step counts in
+// global memory was measured and lost (profiles/r06_dual_xcd_pace_ab.json).
 
 // s_memrealtime ticks (100 MHz): 200 us, ~20-30 producer steps -- a producer that is not
 // running (a shared device, the forced-stall build) turns pacing off instead of stalling MD5.
 constexpr uint64_t kPaceWaitTicks = 20000;
 
-// Where skew group g's producer step count lives in the progress array: the groups of one
-// XCD class side by side, so the eight an MD5 wave follows share one 64-byte line (one L2
-// read per poll).  < kProgressSlots (plan.cpp) for g < 1,024.
-__device__ __forceinline__ uint32_t xcd_progress_slot(uint32_t g) { return (g & 7u) * 128u + (g >> 3); }
-
-// Chains of an MD5 wave in XCD-class order: chain c = c0 + i (c0 = 64 x the wave's index among
-// its class's waves) is part c % 8 of skew group g = xcls + 8 (c / 8), slot 8g + c % 8, over
-// `ngroups` skew groups of 8 slots and `n` slots.  Slots ascend with i, so lane 0 holds the
-// wave's longest part and its last valid lane the shortest, as in a contiguous group.
-struct XcdChains {
-  uint32_t xcls, c0, ngroups, n;
-  __device__ uint32_t slot_of(uint32_t i) const {
-    const uint32_t c = c0 + i;
-    return 8u * (xcls + 8u * (c >> 3)) + (c & 7u);
-  }
-  __device__ uint32_t count() const {  // valid chains (a prefix of the lanes)
-    const uint32_t in_cls = ngroups > xcls ? (ngroups - xcls + 7u) / 8u : 0u;
-    const uint32_t first = c0 >> 3;
-    if (in_cls <= first) return 0;
-    const uint32_t k = in_cls - first < 8u ? in_cls - first : 8u;  // this wave's skew groups
-    const uint32_t end = slot_of(8u * k - 1u) + 1u;                 // the last group may be partial
-    return end <= n ? 8u * k : 8u * k - (end - n);
-  }
-};
-
-// Waits, before the MD5 wave fetches block b0 + B, until the SHA-256 producer(s) of the same
-// parts have published step B / kPaceBps (their loads of B are then issued).  LDS form: the
-// workgroup's own producer counter; global form (kGlobal): the minimum over the wave's skew
-// groups of gprog[group] = (epoch << 32 | steps), another launch's epoch reading as 0, over
-// the lanes that still fetch data of their own part (B < `data_end`, blocks past b0): a lane
-// whose part has ended -- or whose group has nothing in this launch's range -- waits for no
-// producer (its group's producer stops publishing once the group's longest part ends).
-template <uint32_t kPaceBps, bool kGlobal>
+// Waits, before the MD5 wave fetches block b0 + B, until the SHA-256 producer of the same
+// parts has published step B / kPaceBps (its loads of B are then issued): `lds` is the
+// workgroup's producer step counter.  kPaceBps = 0: never waits.
+template <uint32_t kPaceBps>
 struct ShaPacer {
   const uint32_t* lds;
-  const uint64_t* gprog;
-  uint32_t epoch, group;  // global form: this lane's skew group (ignored where !valid)
-  bool valid;
-  uint64_t data_end;  // global form: this lane's part's blocks of data past b0
   uint32_t seen = 0;  // wave-uniform: the last step count read
   bool on = kPaceBps != 0;
   __device__ __forceinline__ void wait_for(uint64_t B) {
     if constexpr (kPaceBps != 0) {
       if (!on) return;
-      const uint32_t need = (B < 2 * kPaceBps ? 1u : uint32_t(B / kPaceBps)) + S3H_EXP_PACE_LAG;
+      const uint32_t need = B < 2 * kPaceBps ? 1u : uint32_t(B / kPaceBps);
       uint64_t t0 = 0;
       while (seen < need) {
-        if constexpr (kGlobal) {
-          // the slowest of this wave's skew groups (a poll only happens when the wave has
-          // caught up with them; its wait for the wave's own loads is then no extra stall)
-          uint32_t m = 0xffffffffu;
-          if (valid && B < data_end) {
-            // agent scope: L2-served (no stale L1 line); the producer is on this XCD
-            const uint64_t v = __hip_atomic_load(gprog + xcd_progress_slot(group), __ATOMIC_RELAXED,
-                                                 __HIP_MEMORY_SCOPE_AGENT);
-            m = uint32_t(v >> 32) == epoch ? uint32_t(v) : 0u;
-          }
-#pragma unroll
-          for (int o = 32; o > 0; o >>= 1) {
-            const uint32_t t = __shfl_xor(m, o);
-            m = t < m ? t : m;
-          }
-          seen = __builtin_amdgcn_readfirstlane(m);
-        } else {
-          seen = __builtin_amdgcn_readfirstlane(
-              __hip_atomic_load(lds, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-        }
+        seen = __builtin_amdgcn_readfirstlane(
+            __hip_atomic_load(lds, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
         if (seen >= need) break;
         const uint64_t now = __builtin_amdgcn_s_memrealtime();
         if (t0 == 0) {
@@ -1749,28 +1622,15 @@ struct ShaPacer {
   }
 };
 
-template <uint32_t kChains, uint32_t kPaceBps = 0, bool kXcd = false>
+template <uint32_t kChains, uint32_t kPaceBps = 0>
 __device__ __forceinline__ void md5_self_body(const LaunchArgs& A, const uint32_t group,
-                                              const uint32_t* pace = nullptr,
-                                              const uint64_t* gprog = nullptr, uint32_t epoch = 0,
-                                              uint32_t nskew = 0) {
-  static_assert(!kXcd || (kChains == 64 && kPaceBps != 0), "XCD-class MD5 waves: 64 paced chains");
+                                              const uint32_t* pace = nullptr) {
   const uint32_t lane = threadIdx.x & 63u;
-  // chains of this wave: slot_of(i) for i < nvalid, ascending in i
-  const XcdChains xc = {blockIdx.x & 7u, 64u * (group >> 3), nskew, A.n};
-  auto slot_of = [&](uint32_t i) -> uint32_t {
-    if constexpr (kXcd) return xc.slot_of(i);
-    else return group * kChains + i;
-  };
-  uint32_t nvalid;
-  if constexpr (kXcd) {
-    nvalid = xc.count();
-  } else {
-    const uint32_t slot0 = group * kChains;
-    nvalid = slot0 >= A.n ? 0u : (A.n - slot0 < kChains ? A.n - slot0 : kChains);
-  }
-  if (nvalid == 0) return;
+  // chains of this wave: slot_of(i) for i < nvalid
+  auto slot_of = [&](uint32_t i) -> uint32_t { return group * kChains + i; };
   const uint32_t slot0 = slot_of(0);
+  const uint32_t nvalid = slot0 >= A.n ? 0u : (A.n - slot0 < kChains ? A.n - slot0 : kChains);
+  if (nvalid == 0) return;
   const bool valid = lane < nvalid;
   const uint32_t slot = valid ? slot_of(lane) : slot0;
   Slot s = {0, 0};
@@ -1797,12 +1657,12 @@ __device__ __forceinline__ void md5_self_body(const LaunchArgs& A, const uint32_
   // last slot is the shortest) take the branch-free fast loop -- decode is one v_perm per
   // word -- so the compiler keeps counted vmcnt waits; the padding blocks at the end run the
   // general decode (its byte loads would otherwise force a full vmcnt drain every block).
-  constexpr uint32_t kDepth = S3H_EXP_MD5_SELF_DEPTH, kRing = kDepth + 1;
+  constexpr uint32_t kDepth = 4, kRing = kDepth + 1;  // blocks fetched ahead
   const uint32_t last = slot_of(nvalid - 1);
   const uint64_t full_end = (A.slots[last].len >> 6) < A.blk_end ? (A.slots[last].len >> 6) : A.blk_end;
   const uint64_t nfast = full_end > b0 ? (full_end - b0) / kRing * kRing : 0;  // whole rings
   RawBlock ring[kRing];
-  ShaPacer<kPaceBps, kXcd> pacer = {pace, gprog, epoch, slot >> 3, valid, fend > b0 ? fend - b0 : 0};
+  ShaPacer<kPaceBps> pacer = {pace};
   auto pace_to = [&](uint64_t B) {  // before fetching block b0 + B
     if (B < iters) pacer.wait_for(B);  // past the range: the zero page, nothing to share
   };
@@ -1869,43 +1729,15 @@ struct Md5Lds {
   uint4 km[2][kBps][16][64];  // [buffer][block of the step][row][lane]: kBps x 32 KiB
 };
 
-// Experiments (timing only, wrong digests): S3H_EXP_MD5_NOSYNC drops every barrier of both
-// waves (consumer speed with the producer's LDS traffic beside it but no waiting for it);
-// S3H_EXP_MD5_NOPROD also removes the producer (the consumer alone).
-#if defined(S3H_EXP_MD5_NOSYNC) || defined(S3H_EXP_MD5_NOPROD)
-#define S3H_MD5_SYNC() ((void)0)
-#else
-#define S3H_MD5_SYNC() __syncthreads()
-#endif
-// kXcd (the split dual grid, sha256_md5_dual_kernel): the workgroup's 64 chains are those of
-// the skew groups on its own XCD (XcdChains over `ngroups` groups), and the producer fetches a
-// step only once those groups' producers have fetched it (ShaPacer, global form) -- one HBM
-// read of every part for both digests.
-template <int kBps, bool kXcd = false>
+template <int kBps>
 __device__ __forceinline__ void md5_pc_body(const LaunchArgs& A, const uint32_t group,
-                                            const uint32_t role, Md5Lds<kBps>& L,
-                                            const uint64_t* gprog = nullptr, uint32_t epoch = 0,
-                                            uint32_t ngroups = 0) {
+                                            const uint32_t role, Md5Lds<kBps>& L) {
   auto& lds_km = L.km;
   const uint32_t lane = threadIdx.x & 63u;
-  const XcdChains xc = {blockIdx.x & 7u, 64u * (group >> 3), ngroups, A.n};
-  uint32_t slot0, slot;  // the first chain's and this lane's slot
-  bool valid;
-  if constexpr (kXcd) {
-    const uint32_t nvalid = xc.count();
-    if (nvalid == 0) return;  // uniform across the workgroup: both waves leave before any barrier
-    slot0 = xc.slot_of(0);
-    valid = lane < nvalid;
-    slot = valid ? xc.slot_of(lane) : slot0;
-  } else {
-    slot0 = group * 64u;
-    slot = slot0 + lane;
-    valid = slot < A.n;
-  }
-  auto last_slot = [&]() -> uint32_t {  // the last valid chain's slot (the shortest part)
-    if constexpr (kXcd) return xc.slot_of(xc.count() - 1);
-    else return (slot0 + 64u <= A.n ? slot0 + 64u : A.n) - 1;
-  };
+  const uint32_t slot0 = group * 64u, slot = slot0 + lane;  // the first chain's and this lane's
+  const bool valid = slot < A.n;
+  // the last valid chain's slot (the shortest part)
+  auto last_slot = [&]() -> uint32_t { return (slot0 + 64u <= A.n ? slot0 + 64u : A.n) - 1; };
   Slot s = {0, 0};
   if (valid) s = A.slots[slot];
   const uint64_t nb = valid ? slot_blocks(A, s.len) : 0;
@@ -1915,9 +1747,6 @@ __device__ __forceinline__ void md5_pc_body(const LaunchArgs& A, const uint32_t 
   const uint64_t iters = wg_end - A.blk_begin;
   const uint64_t nsteps = (iters + kBps - 1) / kBps;  // the same in both waves: equal barriers
 
-#ifdef S3H_EXP_MD5_NOPROD  // experiment (timing only, wrong digests): no producer at all
-  if (role == 1) return;
-#endif
   if (role == 1) {
     // Step k's blocks are fetched one step (kBps blocks, ~5 us of chain time) before they are
     // decoded: two named register sets alternate (no dynamic indexing -> no scratch).
@@ -1934,15 +1763,7 @@ __device__ __forceinline__ void md5_pc_body(const LaunchArgs& A, const uint32_t 
     // wave ran it (MD5 of 300 parts of U[1, 16] MiB: 1.85x the longest chain's time).
     const uint64_t lim = nb < A.blk_end ? nb : A.blk_end;
     RawBlock ra[kBps], rb[kBps];
-    ShaPacer<kXcd ? SkewGeom<1, false>::kBps : 0, true> pacer = {nullptr, gprog, epoch, slot >> 3, valid,
-                                                                 fend > b0 ? fend - b0 : 0};
-    // kXcd: step K's last block, once the skew producers have fetched it
 #define S3H_MD5_FETCH(R, K)                                                                  \
-    if constexpr (kXcd) {                                                                    \
-      if (uint64_t(K) * kBps < iters)                                                        \
-        pacer.wait_for(uint64_t(K) * kBps + kBps - 1 < iters ? uint64_t(K) * kBps + kBps - 1 \
-                                                             : iters - 1);                   \
-    }                                                                                        \
     _Pragma("unroll") for (int h = 0; h < kBps; ++h)                                        \
       fetch_full(p + 64 * ((K) * kBps + h), b0 + (K) * kBps + h < fend, A.zero, R[h]);
 #define S3H_MD5_MAKE_T(R, K, FULL)                                                           \
@@ -1963,25 +1784,25 @@ __device__ __forceinline__ void md5_pc_body(const LaunchArgs& A, const uint32_t 
     // lead is one block (~0.5 us), less than an HBM miss under load: three sets (two blocks
     // ahead) ran 20,480 x 256 KiB at 1,615.5 GiB/s against 1,435.0 with two
     // (profiles/r04_exp_md5_psets.jsonl).
-    constexpr int kSets = kBps == 1 ? S3H_EXP_MD5_PSETS1 : S3H_EXP_MD5_PSETS;
+    constexpr int kSets = kBps == 1 ? 3 : 2;
     if constexpr (kSets == 3) {
     RawBlock rc[kBps];
     S3H_MD5_FETCH(ra, 0)
     S3H_MD5_FETCH(rb, 1)
     S3H_MD5_FETCH(rc, 2)
     S3H_MD5_MAKE(ra, 0)
-    S3H_MD5_SYNC();
+    __syncthreads();
     uint64_t k = 1;  // step s lives in set s % 3: ra, rb, rc
     for (; k + 2 < full_steps; k += 3) {  // steps k, k + 1, k + 2: whole blocks
       S3H_MD5_FETCH(ra, k + 2)
       S3H_MD5_MAKE_T(rb, k, true)
-      S3H_MD5_SYNC();
+      __syncthreads();
       S3H_MD5_FETCH(rb, k + 3)
       S3H_MD5_MAKE_T(rc, k + 1, true)
-      S3H_MD5_SYNC();
+      __syncthreads();
       S3H_MD5_FETCH(rc, k + 4)
       S3H_MD5_MAKE_T(ra, k + 2, true)
-      S3H_MD5_SYNC();
+      __syncthreads();
     }
     // k = 1 (mod 3): the same set roles.  One barrier per step k = 1 .. nsteps, as the
     // consumer's (one after each of its nsteps steps, the first after its state load).
@@ -1990,47 +1811,47 @@ __device__ __forceinline__ void md5_pc_body(const LaunchArgs& A, const uint32_t 
         S3H_MD5_FETCH(ra, k + 2)
         S3H_MD5_MAKE(rb, k)
       }
-      S3H_MD5_SYNC();
+      __syncthreads();
       if (k + 1 > nsteps) break;
       if (k + 1 < nsteps) {
         S3H_MD5_FETCH(rb, k + 3)
         S3H_MD5_MAKE(rc, k + 1)
       }
-      S3H_MD5_SYNC();
+      __syncthreads();
       if (k + 2 > nsteps) break;
       if (k + 2 < nsteps) {
         S3H_MD5_FETCH(rc, k + 4)
         S3H_MD5_MAKE(ra, k + 2)
       }
-      S3H_MD5_SYNC();
+      __syncthreads();
       if (k + 3 > nsteps) break;
     }
     } else {
     S3H_MD5_FETCH(ra, 0)
     S3H_MD5_FETCH(rb, 1)
     S3H_MD5_MAKE(ra, 0)
-    S3H_MD5_SYNC();
+    __syncthreads();
     uint64_t k = 1;
     for (; k + 1 < full_steps; k += 2) {  // steps k and k + 1: whole blocks, both produced
       S3H_MD5_FETCH(ra, k + 1)
       S3H_MD5_MAKE_T(rb, k, true)
-      S3H_MD5_SYNC();
+      __syncthreads();
       S3H_MD5_FETCH(rb, k + 2)
       S3H_MD5_MAKE_T(ra, k + 1, true)
-      S3H_MD5_SYNC();
+      __syncthreads();
     }
     for (;; k += 2) {  // k odd: the same register roles as the loop above
       if (k < nsteps) {
         S3H_MD5_FETCH(ra, k + 1)
         S3H_MD5_MAKE(rb, k)
       }
-      S3H_MD5_SYNC();
+      __syncthreads();
       if (k + 1 > nsteps) break;
       if (k + 1 < nsteps) {
         S3H_MD5_FETCH(rb, k + 2)
         S3H_MD5_MAKE(ra, k + 1)
       }
-      S3H_MD5_SYNC();
+      __syncthreads();
       if (k + 2 > nsteps) break;
     }
     }
@@ -2044,7 +1865,7 @@ __device__ __forceinline__ void md5_pc_body(const LaunchArgs& A, const uint32_t 
       const uint4 v = reinterpret_cast<const uint4*>(A.state + 8ull * A.out_idx[slot])[0];
       st[0] = v.x; st[1] = v.y; st[2] = v.z; st[3] = v.w;
     }
-    S3H_MD5_SYNC();
+    __syncthreads();
     // slots are sorted by length: every chain of the group is live below the last one's end
     const uint32_t last = last_slot();
     const uint64_t live_end = slot_blocks(A, A.slots[last].len);
@@ -2066,28 +1887,19 @@ __device__ __forceinline__ void md5_pc_body(const LaunchArgs& A, const uint32_t 
 #ifdef S3H_MD5_VMEM
       if (kBps == 4 && !check) {  // timing only: rows from a 64 KiB region per workgroup
         md5_step_vmem(st[0], st[1], st[2], st[3], lane * 16u, A.base + 65536ull * group);
-        S3H_MD5_SYNC();
+        __syncthreads();
         return;
       }
 #endif
-#if S3H_EXP_MD5_ROLL
+      // every chain live: the rolling statement (C2 116.8-117.1 GiB/s against 114.2 with the
+      // chunked row reads it replaced, profiles/r03_exp_md5_roll.jsonl)
       if (kBps > 1 && !check) {
         md5_step_roll<(kBps > 1 ? kBps : 2)>(st[0], st[1], st[2], st[3], row_addr(buf, 0));
-        S3H_MD5_SYNC();
+        __syncthreads();
         return;
       }
-#endif
       v4u32 r0 = *reinterpret_cast<const v4u32*>(&lds_km[buf][0][0][lane]);
       v4u32 r1 = *reinterpret_cast<const v4u32*>(&lds_km[buf][0][1][lane]);
-#ifdef S3H_EXP_MD5_NOFUSE  // experiment: the per-block statements in the fast loop too
-      if (false) {
-#else
-      if (kBps > 1 && !check) {
-#endif
-        md5_step_fused<(kBps > 1 ? kBps : 2)>(st[0], st[1], st[2], st[3], r0, r1, row_addr(buf, 0));
-        S3H_MD5_SYNC();
-        return;
-      }
 #pragma unroll
       for (int h = 0; h < kBps; ++h) {
         const uint64_t i = j * kBps + h;
@@ -2112,7 +1924,7 @@ __device__ __forceinline__ void md5_pc_body(const LaunchArgs& A, const uint32_t 
         r0 = n0;
         r1 = n1;
       }
-      S3H_MD5_SYNC();
+      __syncthreads();
     };
     const uint64_t fast = live_end > A.blk_begin ? (live_end - A.blk_begin < iters
                                                     ? live_end - A.blk_begin : iters) : 0;
@@ -2155,25 +1967,19 @@ __global__ __launch_bounds__(kPcThreads) void md5_pc_kernel(LaunchArgs A) {
 // profiles/r01_dual_kernel_trace.txt); one grid of <= 256 workgroups is placed one per CU
 // (profiles/r01_placement.txt).  Used while sha_grid + md5_grid <= #CUs (skew, <= 2,048 parts).
 static_assert(kPcThreads == 128, "dual kernel assumes 128-thread MD5 workgroups");
-// Experiment S3H_EXP_MD5_XCD_PACE (kernel_abi.hpp kMd5XcdPace): the MD5 workgroups take the
-// chains of the skew groups on their own XCD and fetch each step after those groups' producers
-// have (md5_pc_body kXcd; the producers store their step counts to `progress`, tagged with
-// `epoch`), so C2's parts are read from HBM about once for both digests -- measured 0.3 %
-// slower, not the product.  Product: MD5 slots 64w.. per workgroup, unpaced.
+// MD5 workgroup w takes slots 64w.., unpaced: both digests read every part from HBM (pacing the
+// MD5 workgroups by the skew groups of their XCD brought C2's traffic from 2x to 1.04-1.22x but
+// measured 0.3 % slower, profiles/r06_dual_xcd_pace_ab.json).
 template <bool PAIR>
 __global__ __launch_bounds__(128) void sha256_md5_dual_kernel(LaunchArgs S, LaunchArgs M,
-                                                              uint32_t sha_grid, uint64_t* progress,
-                                                              uint32_t epoch) {
+                                                              uint32_t sha_grid) {
   __shared__ SkewLds<1, PAIR> LS;
   __shared__ Md5Lds<2> LM;  // 64 KiB beside the skew group's 36 KiB
   const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  constexpr bool kPaced = kMd5XcdPace && !PAIR;  // XcdChains assumes 8-part skew groups
   if (blockIdx.x < sha_grid)
-    skew_body<1, PAIR, false, false, kPaced>(S, blockIdx.x, wave, LS, nullptr,
-                                             progress ? progress + xcd_progress_slot(blockIdx.x) : nullptr,
-                                             epoch);
+    skew_body<1, PAIR, false>(S, blockIdx.x, wave, LS, nullptr);
   else
-    md5_pc_body<2, kPaced>(M, blockIdx.x - sha_grid, wave, LM, progress, epoch, sha_grid);
+    md5_pc_body<2>(M, blockIdx.x - sha_grid, wave, LM);
 }
 
 // sha256_md5_group_kernel: every workgroup holds BOTH digests of the same kParts parts -- a
@@ -2184,11 +1990,7 @@ __global__ __launch_bounds__(128) void sha256_md5_dual_kernel(LaunchArgs S, Laun
 // the same parts in the same order (plans of the same geometry do: stable sort).
 // The self-fed MD5 wave of a group is paced by its SHA-256 producer (md5_self_body): it
 // fetches each block after the producer has, so the part is read from HBM once.
-#ifdef S3H_EXP_MD5_UNPACED  // experiment: round 3-5's unpaced MD5 wave (every byte read twice)
-template <bool PAIR> constexpr uint32_t kMd5PaceBps = 0;
-#else
 template <bool PAIR> constexpr uint32_t kMd5PaceBps = SkewGeom<1, PAIR>::kBps;
-#endif
 template <bool PAIR>
 __global__ __launch_bounds__(192) void sha256_md5_group_kernel(LaunchArgs S, LaunchArgs M) {
   __shared__ SkewLds<1, PAIR> LS;
@@ -2196,9 +1998,6 @@ __global__ __launch_bounds__(192) void sha256_md5_group_kernel(LaunchArgs S, Lau
   if (threadIdx.x < 2) flags[threadIdx.x] = 0;
   __syncthreads();
   const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-#ifdef S3H_EXP_GROUP_ONLY  // experiment: 1 = SHA-256 group only, 2 = MD5 wave only
-  if ((S3H_EXP_GROUP_ONLY == 1 && wave == 1) || (S3H_EXP_GROUP_ONLY == 2 && wave != 1)) return;
-#endif
   if (wave == 1)
     md5_self_body<SkewGeom<1, PAIR>::kParts, kMd5PaceBps<PAIR>>(M, blockIdx.x, &flags[0]);
   else
@@ -2218,15 +2017,12 @@ __global__ __launch_bounds__(192) void sha256_md5_group_kernel(LaunchArgs S, Lau
 // after the G skewp ones (one self-fed MD5 wave of 64 chains each), so those skew groups run
 // their SHA-256 alone on their CUs (plan.cpp dual_mixed_solo: when that grid fits).  The skewp
 // groups' MD5 waves follow their own producer through LDS (one HBM read of those parts for both
-// digests); the apart MD5 waves run unpaced -- pacing them across workgroups
-// (S3H_EXP_MD5_XCD_PACE: each takes the skew groups of its own XCD and follows their
-// producers' step counts in `progress`, tagged with this launch's `epoch`) cut C3's traffic
-// 1.25x -> 1.18x but cost 3-4 % of its rate.
+// digests); the apart MD5 waves run unpaced -- pacing them across workgroups (each over the
+// skew groups of its own XCD, following their producers' step counts in global memory) cut
+// C3's traffic 1.25x -> 1.18x but cost 3-4 % of its rate (profiles/r06_dual_xcd_pace_ab.json).
 __global__ __launch_bounds__(192) void sha256_md5_group_mixed_kernel(LaunchArgs S, LaunchArgs M,
                                                                     uint32_t F, uint32_t G,
-                                                                    uint32_t lead_md5,
-                                                                    uint64_t* progress,
-                                                                    uint32_t epoch) {
+                                                                    uint32_t lead_md5) {
   __shared__ union {
     SkewLds<1, false> skew;
     SkewLds<1, true> skewp;
@@ -2239,9 +2035,7 @@ __global__ __launch_bounds__(192) void sha256_md5_group_mixed_kernel(LaunchArgs 
   constexpr uint32_t kSolo = SkewGeom<1, false>::kParts;
   if (blockIdx.x < F) {
     if (wave != 1)
-      skew_body<1, false, true, false, kMd5XcdPace && kMd5PaceBps<false> != 0>(
-          S, blockIdx.x, wave >> 1, L.skew, flags,
-          lead_md5 ? progress + xcd_progress_slot(blockIdx.x) : nullptr, epoch);
+      skew_body<1, false, true>(S, blockIdx.x, wave >> 1, L.skew, flags);
     else if (!lead_md5)
       md5_self_body<kSolo, kMd5PaceBps<false>>(M, blockIdx.x, &flags[0]);
     return;
@@ -2249,12 +2043,7 @@ __global__ __launch_bounds__(192) void sha256_md5_group_mixed_kernel(LaunchArgs 
   if (lead_md5 && blockIdx.x >= F + G) {  // MD5 of slots 0 .. 8F-1, 64 chains per workgroup
     if (wave != 1) return;
     M.n = M.n < kSolo * F ? M.n : kSolo * F;
-    if constexpr (kMd5XcdPace && kMd5PaceBps<false> != 0)
-      // lead_md5 = mixed_lead_wgs(F): 8 XCD classes x ceil(F / 64) workgroups, each over the
-      // skew groups that share its XCD, paced by their producers' global step counts
-      md5_self_body<64, kMd5PaceBps<false>, true>(M, blockIdx.x - F - G, nullptr, progress, epoch, F);
-    else
-      md5_self_body<64>(M, blockIdx.x - F - G);  // slots 64w.., unpaced (the product)
+    md5_self_body<64>(M, blockIdx.x - F - G);  // slots 64w.., unpaced
     return;
   }
   const uint32_t shift = kSolo * F;

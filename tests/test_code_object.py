@@ -140,22 +140,44 @@ def test_no_kernel_uses_scratch():
         assert m["vgpr_spill_count"] == 0, (sym, m)
 
 
-@pytest.mark.parametrize("flags,ok", [([], True), (["-DS3H_EXP_SOLO=3"], False),
-                                      (["-DS3H_EXP_MD5_BPS=2"], False),
-                                      (["-DS3H_EXP_NONTEMPORAL_FETCH"], False),
-                                      (["-DS3H_EXPERIMENT_BUILD", "-DS3H_EXP_SOLO=3",
-                                        "-DS3H_EXP_MD5_BPS=2"], True)])
+@pytest.mark.parametrize("flags,ok", [([], True), (["-DS3H_EXP_SHA1_BPS=1"], False),
+                                      (['-DS3H_EXP_PRODUCER_INC="other_producer.inc"'], False),
+                                      (["-DS3H_EXP_STALL_PRODUCER=1"], False),
+                                      (["-DS3H_EXPERIMENT_BUILD", "-DS3H_EXP_SHA1_BPS=1",
+                                        '-DS3H_EXP_PRODUCER_INC="other_producer.inc"',
+                                        "-DS3H_EXP_STALL_PRODUCER=1"], True)])
 def test_product_build_refuses_experiment_switches(tmp_path, flags, ok):
     """exp_config.hpp: a build without S3H_EXPERIMENT_BUILD (the shipped libs3hash.so) must keep
     every experiment switch at its product value -- the kernels measured in DESIGN.md and
     hashed in kernel_isa_counts.json; `make exp` / `make stall` builds opt out explicitly."""
     import subprocess
     src = tmp_path / "t.cpp"
-    src.write_text('#include "exp_config.hpp"\nint main() { return S3H_EXP_MD5_BPS; }\n')
+    src.write_text('#include "exp_config.hpp"\nint main() { return S3H_EXP_SHA1_BPS; }\n')
     r = subprocess.run(["g++", "-std=c++17", "-fsyntax-only",
                         "-I" + os.path.join(ROOT, "s3client_amd", "csrc"), *flags, str(src)],
                        capture_output=True, text=True)
     assert (r.returncode == 0) == ok, r.stderr[-1500:]
+
+
+def test_every_switch_is_declared_and_every_declared_switch_is_used():
+    """A switch whose experiment has been decided is deleted with the code it selected, not
+    left switched off: the S3H_EXP_* names (and the two the generated .inc files define) that
+    the sources under s3client_amd/csrc mention, comments included, are exactly the ones
+    exp_config.hpp defines or guards."""
+    import re
+    name = re.compile(r"\b(S3H_EXP_\w+|S3H_PROD_ZYV|S3H_MD5_VMEM)\b")
+    csrc = os.path.join(ROOT, "s3client_amd", "csrc")
+    used = set()
+    for d, _, files in os.walk(csrc):
+        for f in files:
+            if f != "exp_config.hpp":
+                with open(os.path.join(d, f), errors="replace") as fh:
+                    used |= set(name.findall(fh.read()))
+    with open(os.path.join(csrc, "exp_config.hpp")) as fh:
+        code = "\n".join(l.split("//")[0] for l in fh)
+    declared = set(name.findall(code))
+    assert used == declared, (sorted(used - declared), sorted(declared - used))
+    assert "S3H_EXP_STALL_PRODUCER" in declared and len(declared) >= 5  # the scan found them
 
 
 def test_power_sampler_reports_instead_of_failing():

@@ -171,7 +171,8 @@ def test_dual_digest_device_on_stream(torch_cuda, n, lo, form):
     assert (info["dual_solo"] > 0) == (form == "mixed")
     if form in ("split", "group-skew"):
         assert info["kernel"] == "skew" and info["grid"] == (n + 7) // 8 <= cus
-        # the split grid adds its MD5 workgroups (kernel_abi.hpp split_md5_wgs, either pacing)
+        # the split grid adds its MD5 workgroups (kernel_abi.hpp split_md5_wgs: one per 64
+        # parts); the cases keep the same side of the limit with that count rounded up to 8s
         for md5_wgs in (8 * ((info["grid"] + 63) // 64), (n + 63) // 64):
             assert (info["grid"] + md5_wgs <= cus) == (form == "split")
     elif form == "two-kernels":

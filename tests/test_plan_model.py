@@ -21,7 +21,7 @@ def test_mixed_grid_forms():
 
 def test_lengths_between_the_two_ratios_keep_a_mixed_grid():
     """Every part within 2650/2224 of the longest but some within 2650/2280 (the planning rates,
-    exp_config.hpp): the apart form would need a skew group for every part, round 3's form needs
+    plan.cpp): the apart form would need a skew group for every part, round 3's form needs
     one (advisor r4: the loop returned 0 instead of trying the smaller ratio)."""
     lens = [L0] + [int(L0 * 0.85)] * 2099
     assert s3.dual_layout(lens) == (1, False)

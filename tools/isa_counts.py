@@ -31,8 +31,8 @@ KERNELS = {
     "skew_nc2": ("_ZN3s3h24sha256_skew_pairs_kernelENS_10LaunchArgsE", 8),
     "skewp": ("_ZN3s3h18sha256_skew_kernelILi1ELb1EEEvNS_10LaunchArgsE", 4),
     "skews": ("_ZN3s3h25sha256_skew_shared_kernelENS_10LaunchArgsE", 8),
-    "md5-pc": ("_ZN3s3h13md5_pc_kernelILi4EEEvNS_10LaunchArgsE", 4),  # S3H_EXP_MD5_BPS
-    "sha1-pc": ("_ZN3s3h14sha1_pc_kernelILi2EEEvNS_10LaunchArgsE", 2),  # S3H_EXP_SHA1_BPS
+    "md5-pc": ("_ZN3s3h13md5_pc_kernelILi4EEEvNS_10LaunchArgsE", 4),  # kernel_abi.hpp kMd5Bps
+    "sha1-pc": ("_ZN3s3h14sha1_pc_kernelILi2EEEvNS_10LaunchArgsE", 2),  # kernel_abi.hpp kSha1Bps
     "sha1-pc1": ("_ZN3s3h14sha1_pc_kernelILi1EEEvNS_10LaunchArgsE", 1),
 }
 # every kernel a plan can launch (code hashes) and the flag-synchronised ones among them, whose
@@ -47,10 +47,10 @@ ALL_KERNELS = {
     "skewp": KERNELS["skewp"][0], "skews": KERNELS["skews"][0],
     "md5-pc": "_ZN3s3h13md5_pc_kernelILi4EEEvNS_10LaunchArgsE",
     "md5-pc1": "_ZN3s3h13md5_pc_kernelILi1EEEvNS_10LaunchArgsE",
-    "dual_split": "_ZN3s3h22sha256_md5_dual_kernelILb0EEEvNS_10LaunchArgsES1_jPmj",
+    "dual_split": "_ZN3s3h22sha256_md5_dual_kernelILb0EEEvNS_10LaunchArgsES1_j",
     "dual_group": "_ZN3s3h23sha256_md5_group_kernelILb1EEEvNS_10LaunchArgsES1_",
     "dual_group_skew": "_ZN3s3h23sha256_md5_group_kernelILb0EEEvNS_10LaunchArgsES1_",
-    "dual_group_mixed": "_ZN3s3h29sha256_md5_group_mixed_kernelENS_10LaunchArgsES0_jjjPmj",
+    "dual_group_mixed": "_ZN3s3h29sha256_md5_group_mixed_kernelENS_10LaunchArgsES0_jjj",
     # CRC-32C / CRC-32 (crc32_kernels.hip): code hashes only, no chain loop to count
     "crc_segments": "_ZN3s3h19crc_segments_kernelENS_10CrcSegArgsE",
     "crc_parts": "_ZN3s3h16crc_parts_kernelENS_11CrcPartArgsE",
